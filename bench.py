@@ -1,6 +1,7 @@
 """Benchmark: ICP iterations/s and matched-pairs/s on the BASELINE.json workload.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c3] [--matcher brute] [--scaling strong|weak]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                    [--config c3] [--matcher brute] [--scaling strong|weak]
 
 A "step" is one ICP iteration of the hot path — fused transform + k-NN
 match, outlier weighting, normal equations, the 6x6 solve and the checker —
@@ -13,15 +14,25 @@ reference (strong scaling, the north_star "1M->1M at 1/2/4/8 MI355X"; weak:
 window segments (all-gather) and the normal equations (all-reduce) over RCCL.
 
 Timing: W untimed iterations, then exactly K iterations between a barrier +
-device synchronisation on both sides; the max over ranks is reported.  The
-clouds are resident in HBM before the timed region.  The match kernel's
-device time is measured with HIP events on the context stream (pmx_timing_*).
-Every run also times one whole ICP from the initial pose (`whole_icp`: 40
-iterations of the same chain, the work the CPU baseline times, cold first
-match included).  The CPU baseline (rank 0, N = 1 only) is the oracle's
-libnabo-style kd-tree restatement of the reference CPU path on the same
-inputs, built -march=native on this host, on every core the job may use and
-on one thread.
+device synchronisation on both sides; the max over ranks is reported
+(`value`, `ms_per_step`).  The clouds are resident in HBM before the timed
+region, and a short untimed device warm-up brings the GPU to its working
+clocks.  A plain run does no more than that.  --dump-outputs DIR then writes
+what the timed steps computed: DIR/T.npy, the transform a caller of prepare /
+iterate / finish receives after the last timed step, and DIR/last_step.npy
+(float64: iterations run, pairs kept, weighted and plain point-used ratios of
+the last step).  The inputs are seeded, so two runs with the same arguments
+time and dump the same computation.
+
+--full adds every other measurement to the result line: the per-compute setup
+(`setup_ms`), one whole ICP from the initial pose (`whole_icp`: 40 iterations
+of the same chain, the work the CPU baseline times, cold first match
+included), ICPSequence, the match kernel's device time measured with HIP
+events on the context stream (pmx_timing_*, `roofline`), and the CPU baseline
+with its parity checks (rank 0, N = 1 only; --no-cpu-baseline leaves it out):
+the oracle's libnabo-style kd-tree restatement of the reference CPU path on
+the same inputs, built -march=native on this host, on every core the job may
+use and on one thread.
 """
 from __future__ import annotations
 
@@ -51,6 +62,7 @@ BASELINE_CONFIGS = ("c2", "c3", "c4", "c5")
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E (MI355X_MICROARCH.md)
 FP32_VALU_TFLOPS = 157.3   # MI355X FP32 vector peak (spec)
 FP64_VALU_TFLOPS = 78.6
+DIAG_RING = 1024           # iterations pmx_icp_loop_diag can look back
 
 
 def chain_yaml(knn, filters, minimizer, search_type, maxit, differential=None):
@@ -208,6 +220,13 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong: the configuration's global reading split over the ranks (default); "
                          "weak: the configuration's reading on every rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-compute setup, one whole ICP "
+                         "from the initial pose, ICPSequence, the roofline pass and (one GPU) the CPU baseline with "
+                         "its parity checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (the transform a caller of prepare / "
+                         "iterate / finish receives, and the last step's pair counts) as DIR/<name>.npy")
     ap.add_argument("--cpu-iters", type=int, default=40)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-one-thread-cap", type=float, default=100.0,
@@ -327,58 +346,62 @@ def main():
         # (every rank runs the same number: the sharded ICP exchanges collectives)
         if max_over_ranks(1.0 if time.perf_counter() >= w_end else 0.0) > 0.0:
             break
-    # setup: the per-compute cost on the live, warm context — the best of
-    # three prepares after the device warm-up, with its reference / reading
-    # parts from that prepare's statistics
-    setup_s, setup_parts = None, None
-    for _ in range(3):
-        barrier()
-        t_s = time.perf_counter()
-        icp.prepare(reading, reference, nrm_in)
-        dt = max_over_ranks(time.perf_counter() - t_s)
-        if setup_s is None or dt < setup_s:
-            pst = icp.stats()
-            setup_s = dt
-            setup_parts = {"reference_ms": 1e3 * pst.reference_preprocessing_duration,
-                           "reading_ms": 1e3 * pst.reading_preprocessing_duration}
+    # ---- --full only, before the driver region: the per-compute setup, one
+    # whole ICP from the initial pose and ICPSequence
+    setup_s, setup_parts, whole = None, None, None
+    if args.full:
+        # setup: the per-compute cost on the live, warm context — the best of
+        # three prepares after the device warm-up, with its reference / reading
+        # parts from that prepare's statistics
+        for _ in range(3):
+            barrier()
+            t_s = time.perf_counter()
+            icp.prepare(reading, reference, nrm_in)
+            dt = max_over_ranks(time.perf_counter() - t_s)
+            if setup_s is None or dt < setup_s:
+                pst = icp.stats()
+                setup_s = dt
+                setup_parts = {"reference_ms": 1e3 * pst.reference_preprocessing_duration,
+                               "reading_ms": 1e3 * pst.reading_preprocessing_duration}
 
-    # ---- one whole ICP from the initial pose (the representative workload:
-    # what every new scan pays, and what the CPU baseline times): the timing
-    # chain of the CPU baseline (Counter cpu_iters), prepare untimed
-    icp.prepare(reading, reference, nrm_in)
-    barrier()
-    w0 = time.perf_counter()
-    icp.iterate(args.cpu_iters)
-    w1 = time.perf_counter()
-    barrier()
-    whole_s = max_over_ranks(w1 - w0)
-    wst = icp.stats()
-    hits, misses = icp.select_stats()
-    # the same ICP once more, one iteration per call with HIP events around
-    # each match: the cold first match and the matches of the first iterations
-    icp.prepare(reading, reference, nrm_in)
-    first_match_us = []
-    for _ in range(min(8, args.cpu_iters)):
-        icp.timing(True)
-        icp.iterate(1)
-        ms, nl = icp.timing_read()
-        first_match_us.append(round(1e3 * ms / max(nl, 1), 2))
-    icp.timing(False)
-    whole = {"iterations": int(wst.iterations), "ms": 1e3 * whole_s,
-             "ms_per_iteration": 1e3 * whole_s / max(int(wst.iterations), 1),
-             "matched_pairs_per_s": N_work * knn * int(wst.iterations) / whole_s,
-             "cold_match_ms": first_match_us[0] * 1e-3 if first_match_us else None,
-             "first_matches_us": first_match_us,
-             "window_hits": int(hits), "window_misses": int(misses),
-             "chain": f"the workload's chain, CounterTransformationChecker {args.cpu_iters}, from the initial pose "
-                      f"(prepare untimed, then {args.cpu_iters} iterations timed as the CPU baseline's loop); "
-                      f"first_matches_us: device time of each of the first matches (separate run, HIP events)",
-             "device_warmup": f"{n_warm} untimed whole ICPs ({args.device_warmup:.2f} s) before every measured region"}
+        # ---- one whole ICP from the initial pose (the representative workload:
+        # what every new scan pays, and what the CPU baseline times): the timing
+        # chain of the CPU baseline (Counter cpu_iters), prepare untimed
+        icp.prepare(reading, reference, nrm_in)
+        barrier()
+        w0 = time.perf_counter()
+        icp.iterate(args.cpu_iters)
+        w1 = time.perf_counter()
+        barrier()
+        whole_s = max_over_ranks(w1 - w0)
+        wst = icp.stats()
+        hits, misses = icp.select_stats()
+        # the same ICP once more, one iteration per call with HIP events around
+        # each match: the cold first match and the matches of the first iterations
+        icp.prepare(reading, reference, nrm_in)
+        first_match_us = []
+        for _ in range(min(8, args.cpu_iters)):
+            icp.timing(True)
+            icp.iterate(1)
+            ms, nl = icp.timing_read()
+            first_match_us.append(round(1e3 * ms / max(nl, 1), 2))
+        icp.timing(False)
+        whole = {"iterations": int(wst.iterations), "ms": 1e3 * whole_s,
+                 "ms_per_iteration": 1e3 * whole_s / max(int(wst.iterations), 1),
+                 "matched_pairs_per_s": N_work * knn * int(wst.iterations) / whole_s,
+                 "cold_match_ms": first_match_us[0] * 1e-3 if first_match_us else None,
+                 "first_matches_us": first_match_us,
+                 "window_hits": int(hits), "window_misses": int(misses),
+                 "chain": f"the workload's chain, CounterTransformationChecker {args.cpu_iters}, from the initial pose "
+                          f"(prepare untimed, then {args.cpu_iters} iterations timed as the CPU baseline's loop); "
+                          f"first_matches_us: device time of each of the first matches (separate run, HIP events)",
+                 "device_warmup": f"{n_warm} untimed whole ICPs ({args.device_warmup:.2f} s) before every measured "
+                                  f"region"}
 
     # ---- ICPSequence (before the driver region: the last dispatches of the
     # command are the timed pass and the roofline pass, tools/pmc_phases.py)
     seq_ms, seq_note = None, None
-    if not dist:
+    if args.full and not dist:
         # ICPSequence (ICP.cpp:455-609): the map set once, then each scan pays
         # only the reading side (upload, slot order) and its iterations
         from libpointmatcher_amd.icp import ICPSequence
@@ -417,63 +440,28 @@ def main():
     # per-iteration evidence of the timed iterations (pmx_loop_diag): the grid
     # level each match ran on, the quantile window verdict, the pairs
     # evaluated and the full searches (the rest certified by temporal reuse)
-    dg = icp.loop_diag(0, args.warmup + args.steps)[args.warmup:]
+    # (the library keeps the last DIAG_RING iterations: of a longer run, the last timed ones)
+    n_diag = min(args.steps, DIAG_RING)
+    dg = icp.loop_diag(args.warmup + args.steps - n_diag, n_diag)
     diag = {"levels": [int(x) for x in dg[:, 0]], "window": [int(x) for x in dg[:, 1]],
             "pairs_evaluated": [int(x) for x in dg[:, 2]], "full_searches": [int(x) for x in dg[:, 3]],
-            "note": "timed iterations only: grid level index of each match (0 = the finest; DESIGN.md §3), "
-                    "window 1 = quantile resolved in the match's key window, 0 = radix passes, -1 = no window"}
+            "note": f"timed iterations only (the last {DIAG_RING} of a longer run): grid level index of each match "
+                    "(0 = the finest; DESIGN.md §3), window 1 = quantile resolved in the match's key window, 0 = radix passes, -1 = no window"}
     # collectives and host synchronisations of the timed iterations (sharded
     # runs: stall-and-replay)
     comm = ({k: v - cs0[k] for k, v in icp.comm_stats().items()} if dist else None)
-    # Roofline pass: the same ICP again (prepare resets the pose and the
-    # match history), now with HIP events around every match launch on the
-    # context stream.  The events are kept out of the timed region above: each
-    # record is a marker packet that adds idle GPU time to the iteration.
-    icp.prepare(reading, reference, nrm_in)
-    if args.warmup > 0:
-        icp.iterate(args.warmup)
-    icp.timing(True)
-    icp.iterate(args.steps)
-    match_ms, launches = icp.timing_read()
-    icp.timing(False)
+    if int(st.iterations) != args.warmup + args.steps:
+        sys.exit(f"bench: {int(st.iterations)} iterations ran, not the {args.warmup} + {args.steps} asked for")
+    if args.dump_outputs and rank == 0:
+        # what the timed path computed: the transform after the last timed
+        # step (every rank holds the same one) and that step's pair counts
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "T.npy"), np.asarray(icp.finish(), dtype))
+        np.save(os.path.join(args.dump_outputs, "last_step.npy"),
+                np.array([st.iterations, st.kept, st.overlap_ratio, st.point_used_ratio], np.float64))
 
     pairs = N_work * knn * args.steps
-    avg_match_s = match_ms * 1e-3 / max(launches, 1)
     esz = np.dtype(dtype).itemsize
-    # algorithmic bytes of one match launch: the reading shard (4 T per point),
-    # the reference (4 T per point) and the k (dist, id) outputs per query
-    alg_bytes = N * 4 * esz + M * 4 * esz + N * knn * (esz + 4)
-    alg_bytes_survey = alg_bytes  # N*16 + M*16 + N*k*8 (fp32; doubled for fp64 but the ids)
-    # pair evaluations per match launch: N*M for brute force, the measured
-    # PointCountTouched per iteration for the grid search
-    # (the timed iterations' own pairs, from the per-iteration record)
-    pairs_eval = N * M if args.matcher == "brute" else float(dg[:, 2].mean())
-    flops = 8.0 * pairs_eval  # 3 sub + 3 mul + 2 add per pair
-    if args.matcher == "grid":
-        # the grid adds the order / id / cell-range traffic: ids (4 B) of every
-        # reference point and the visit order (4 B) of every query
-        alg_bytes += N * 4 + M * 4
-    achieved_gbs = alg_bytes_survey / avg_match_s / 1e9
-    achieved_grid_gbs = alg_bytes / avg_match_s / 1e9
-    # HBM traffic of the match kernel from the committed PMC passes of this
-    # exact command (tools/pmc_phases.py: FETCH_SIZE x2 (gfx950 correction) +
-    # WRITE_SIZE per launch, averaged over the launches of the timed steps);
-    # null for other configurations
-    traffic, traffic_src = None, None
-    if args.matcher == "grid" and world == 1:
-        for src in (os.path.join("profiles", "r06", f"pmc_{args.config}_driver.json"),
-                    os.path.join("profiles", "r05", f"pmc_{args.config}_driver.json"),
-                    os.path.join("profiles", "r04", f"pmc_{args.config}_driver.json"),
-                    os.path.join("profiles", "r03", f"pmc_{args.config}_driver.json")):
-            try:
-                with open(os.path.join(ROOT, src)) as f:
-                    pm = json.load(f)
-                traffic = pm["match"]["timed"]["hbm_bytes_per_launch"]
-                traffic_src = src
-                break
-            except (OSError, KeyError, TypeError, ValueError):
-                pass
-    peak_tf = FP32_VALU_TFLOPS if esz == 4 else FP64_VALU_TFLOPS
     metric = "ICP iterations/sec + matched-pairs/sec, 1M→1M pts, k=1, point-to-plane"
     try:
         with open(os.path.join(ROOT, "BASELINE.json")) as f:
@@ -511,7 +499,86 @@ def main():
         "comm_timed": comm,
         "kept_pairs_last_iter": st.kept,
         "timed_iterations": diag,
-        "whole_icp": whole,
+        "first_prepare_ms": first_prepare_s * 1e3,
+        "device_warmup": f"{n_warm} untimed whole ICPs ({args.device_warmup:.2f} s) before the timed steps",
+    }
+    if args.full:
+        result["whole_icp"] = whole
+        result.update(roofline_pass(args, icp, reading, reference, nrm_in, N, M, knn, esz, dg, world))
+        result["setup_ms"] = setup_s * 1e3
+        if seq_ms is not None:
+            result["sequence_scan_ms"] = seq_ms
+            result["sequence_scan_note"] = seq_note
+        result["setup_parts"] = setup_parts
+        result["setup_note"] = ("ICP::compute setup before the first iteration, on a live device context (best of "
+                                "three prepares after the device warm-up): reference mean (host thread, T-sequential) "
+                                "+ upload + centring, Matcher::init (the cold grid level; the finer ones on a side "
+                                "stream, awaited by the second match), reading upload (overlapping the level build) + "
+                                "Morton slot order (device sort); first_prepare_ms adds the context creation (HIP "
+                                "runtime, code objects)")
+        if rank == 0 and world == 1 and args.emulate_ranks == 1 and not args.no_cpu_baseline:
+            cpu_parity(args, result, icp, reading, reference, normals, nrm_in, knn, filters, minimizer, search_type,
+                       esz)
+        else:
+            result["cpu_baseline"] = None
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    icp.close()
+    if dist:
+        tdist.destroy_process_group()
+
+
+def roofline_pass(args, icp, reading, reference, nrm_in, N, M, knn, esz, dg, world):
+    """--full: the timed region once more with HIP events around every match
+    launch; returns the result line's roofline and compute_roofline blocks."""
+    # Roofline pass: the same ICP again (prepare resets the pose and the
+    # match history), now with HIP events around every match launch on the
+    # context stream.  The events are kept out of the timed region: each
+    # record is a marker packet that adds idle GPU time to the iteration.
+    icp.prepare(reading, reference, nrm_in)
+    if args.warmup > 0:
+        icp.iterate(args.warmup)
+    icp.timing(True)
+    icp.iterate(args.steps)
+    match_ms, launches = icp.timing_read()
+    icp.timing(False)
+
+    avg_match_s = match_ms * 1e-3 / max(launches, 1)
+    # algorithmic bytes of one match launch: the reading shard (4 T per point),
+    # the reference (4 T per point) and the k (dist, id) outputs per query
+    alg_bytes = N * 4 * esz + M * 4 * esz + N * knn * (esz + 4)
+    alg_bytes_survey = alg_bytes  # SURVEY.md §8(d): N*16 + M*16 + N*k*8 (fp32; doubled for fp64 but the ids)
+    # pair evaluations per match launch: N*M for brute force, the measured
+    # PointCountTouched per iteration for the grid search
+    # (the timed iterations' own pairs, from the per-iteration record)
+    pairs_eval = N * M if args.matcher == "brute" else float(dg[:, 2].mean())
+    flops = 8.0 * pairs_eval  # 3 sub + 3 mul + 2 add per pair
+    if args.matcher == "grid":
+        # the grid adds the order / id / cell-range traffic: ids (4 B) of every
+        # reference point and the visit order (4 B) of every query
+        alg_bytes += N * 4 + M * 4
+    achieved_gbs = alg_bytes_survey / avg_match_s / 1e9
+    achieved_grid_gbs = alg_bytes / avg_match_s / 1e9
+    # HBM traffic of the match kernel from the committed PMC passes of this
+    # exact command (tools/pmc_phases.py: FETCH_SIZE x2 (gfx950 correction) +
+    # WRITE_SIZE per launch, averaged over the launches of the timed steps);
+    # null for other configurations
+    traffic, traffic_src = None, None
+    if args.matcher == "grid" and world == 1:
+        for src in (os.path.join("profiles", "r06", f"pmc_{args.config}_driver.json"),
+                    os.path.join("profiles", "r05", f"pmc_{args.config}_driver.json"),
+                    os.path.join("profiles", "r04", f"pmc_{args.config}_driver.json"),
+                    os.path.join("profiles", "r03", f"pmc_{args.config}_driver.json")):
+            try:
+                with open(os.path.join(ROOT, src)) as f:
+                    pm = json.load(f)
+                traffic = pm["match"]["timed"]["hbm_bytes_per_launch"]
+                traffic_src = src
+                break
+            except (OSError, KeyError, TypeError, ValueError):
+                pass
+    peak_tf = FP32_VALU_TFLOPS if esz == 4 else FP64_VALU_TFLOPS
+    blocks = {
         "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic,
                      "achieved_with_grid_bytes": achieved_grid_gbs, "frac_with_grid_bytes": achieved_grid_gbs / HBM_PEAK_GBS,
@@ -538,56 +605,44 @@ def main():
                              "note": "brute-force match is VALU-bound (8 FLOP/pair); the HBM fraction is small by construction"},
     }
     if args.matcher == "grid":
-        result["compute_roofline"]["note"] = ("grid search: FLOP counts only the pairs actually evaluated; the kernel "
+        blocks["compute_roofline"]["note"] = ("grid search: FLOP counts only the pairs actually evaluated; the kernel "
                                               "is gather-latency-bound, neither VALU- nor HBM-bandwidth-bound")
-    result["setup_ms"] = setup_s * 1e3
-    if seq_ms is not None:
-        result["sequence_scan_ms"] = seq_ms
-        result["sequence_scan_note"] = seq_note
-    result["setup_parts"] = setup_parts
-    result["first_prepare_ms"] = first_prepare_s * 1e3
-    result["setup_note"] = ("ICP::compute setup before the first iteration, on a live device context (best of three "
-                            "prepares after the device warm-up): reference mean (host thread, T-sequential) + "
-                            "upload + centring, Matcher::init (the cold grid level; the finer ones on a side stream, "
-                            "awaited by the second match), reading upload (overlapping the level build) + Morton slot "
-                            "order (device sort); first_prepare_ms adds the context creation (HIP runtime, code objects)")
-    if rank == 0 and world == 1 and args.emulate_ranks == 1 and not args.no_cpu_baseline:
-        threads = args.cpu_threads or usable_cores()[0]
-        # GPU side of the parity checks: whole ICPs from the initial pose
-        # with the timing chain and with the parity chain (same inputs)
-        gpu = {}
-        for name, diff in (("counter", None), ("differential", PARITY_DIFF)):
-            icp.load_yaml(chain_yaml(knn, filters, minimizer, search_type, args.cpu_iters, diff))
-            gpu[name] = (icp.compute(reading, reference, nrm_in), icp.stats())
-        cb, runs = cpu_baseline(args.config, reading, reference, normals, knn, filters, minimizer,
-                                args.cpu_iters, threads, args.cpu_one_thread_cap)
-        result["cpu_baseline"] = cb
-        if runs is not None:
-            tol = 1e-5 if esz == 4 else 1e-12
-            par = {"counter": parity_entry(*gpu["counter"], runs["counter"], tol,
-                                           f"the workload's chain, Counter {args.cpu_iters}")}
-            if "differential" in runs:
-                par["differential"] = parity_entry(*gpu["differential"], runs["differential"], tol,
-                                                   f"+ DifferentialTransformationChecker {PARITY_DIFF}")
-            par["pass"] = all(v["pass"] for v in par.values() if isinstance(v, dict))
-            if "counter_Tsums" in runs:
-                TT = np.asarray(runs["counter_Tsums"]["T"], np.float64)
-                par["accumulation_gap"] = {
-                    "frob_cpu_f64sums_vs_cpu_Tsums": float(np.linalg.norm(np.asarray(runs["counter"]["T"],
-                                                                                     np.float64) - TT)),
-                    "frob_gpu_vs_cpu_Tsums": float(np.linalg.norm(np.asarray(gpu["counter"][0], np.float64) - TT)),
-                    "note": "GPU and oracle sum the normal equations in fp64 from T products; the reference sums "
-                            "in T (Eigen GEMM): the size of that deliberate difference here (Counter chain)"}
-            result["parity"] = par
-            if cb:
-                result["whole_icp"]["vs_cpu_all_cores"] = whole["matched_pairs_per_s"] / cb["value"]
-    else:
-        result["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    icp.close()
-    if dist:
-        tdist.destroy_process_group()
+    return blocks
+
+
+def cpu_parity(args, result, icp, reading, reference, normals, nrm_in, knn, filters, minimizer, search_type, esz):
+    """--full, one GPU: the CPU baseline on the same inputs and the parity of
+    whole GPU ICPs with it; fills cpu_baseline, parity and
+    whole_icp.vs_cpu_all_cores of the result line."""
+    threads = args.cpu_threads or usable_cores()[0]
+    # GPU side of the parity checks: whole ICPs from the initial pose
+    # with the timing chain and with the parity chain (same inputs)
+    gpu = {}
+    for name, diff in (("counter", None), ("differential", PARITY_DIFF)):
+        icp.load_yaml(chain_yaml(knn, filters, minimizer, search_type, args.cpu_iters, diff))
+        gpu[name] = (icp.compute(reading, reference, nrm_in), icp.stats())
+    cb, runs = cpu_baseline(args.config, reading, reference, normals, knn, filters, minimizer,
+                            args.cpu_iters, threads, args.cpu_one_thread_cap)
+    result["cpu_baseline"] = cb
+    if runs is not None:
+        tol = 1e-5 if esz == 4 else 1e-12
+        par = {"counter": parity_entry(*gpu["counter"], runs["counter"], tol,
+                                       f"the workload's chain, Counter {args.cpu_iters}")}
+        if "differential" in runs:
+            par["differential"] = parity_entry(*gpu["differential"], runs["differential"], tol,
+                                               f"+ DifferentialTransformationChecker {PARITY_DIFF}")
+        par["pass"] = all(v["pass"] for v in par.values() if isinstance(v, dict))
+        if "counter_Tsums" in runs:
+            TT = np.asarray(runs["counter_Tsums"]["T"], np.float64)
+            par["accumulation_gap"] = {
+                "frob_cpu_f64sums_vs_cpu_Tsums": float(np.linalg.norm(np.asarray(runs["counter"]["T"],
+                                                                                 np.float64) - TT)),
+                "frob_gpu_vs_cpu_Tsums": float(np.linalg.norm(np.asarray(gpu["counter"][0], np.float64) - TT)),
+                "note": "GPU and oracle sum the normal equations in fp64 from T products; the reference sums "
+                        "in T (Eigen GEMM): the size of that deliberate difference here (Counter chain)"}
+        result["parity"] = par
+        if cb:
+            result["whole_icp"]["vs_cpu_all_cores"] = result["whole_icp"]["matched_pairs_per_s"] / cb["value"]
 
 
 if __name__ == "__main__":

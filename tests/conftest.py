@@ -28,7 +28,9 @@ def golden():
     import json
 
     import numpy as np
+    # (two files: each committed fixture stays under 1 MiB)
     g = dict(np.load(os.path.join(TESTS, "golden", "clouds.npz")))
+    g.update(np.load(os.path.join(TESTS, "golden", "clouds_vtk.npz")))
     with open(os.path.join(TESTS, "golden", "kat.json")) as f:
         kat = json.load(f)
     return g, kat

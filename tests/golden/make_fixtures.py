@@ -1,12 +1,14 @@
 """Generate the committed golden fixtures from the reference's own test data.
 
-Run once in the build container (where /root/reference exists):
-    python tests/golden/make_fixtures.py
+Run once, with the reference's examples/data directory:
+    python tests/golden/make_fixtures.py <reference>/examples/data
 Outputs (data only, no reference source) go to tests/golden/:
-  - clouds.npz: the point clouds the reference's tests load
+  - clouds.npz, clouds_vtk.npz: the point clouds the reference's tests load
       (examples/data/car_cloud400.csv [with nx,ny,nz], car_cloud401.csv,
-       2D_oneBox.csv, 2D_twoBoxes.csv, cloud.00000.vtk, cloud.00001.vtk),
+       2D_oneBox.csv, 2D_twoBoxes.csv; cloud.00000.vtk, cloud.00001.vtk),
       stored as float32 (n, D) arrays;
+  - data/: car_cloud400.csv and cloud.00000.vtk (gzip) and 2D_oneBox.csv as
+      they are, for the .csv / .vtk loaders' test;
   - kat.json: known answers transcribed from the reference tests
       (utest/utest.cpp:346-356 validT2d/validT3d; utest/utest.h:49-85
        tolerances; utest/ui/Outliers.cpp:126-152 VarTrimmed KAT), the
@@ -14,13 +16,16 @@ Outputs (data only, no reference source) go to tests/golden/:
       icp_data/*.yaml chain configurations they are the answers for (test
       inputs of utest.cpp:81-160, loaded unchanged by the GPU chain).
 """
+import gzip
 import json
 import os
 import re
+import shutil
+import sys
 
 import numpy as np
 
-REF = "/root/reference/examples/data"
+REF = sys.argv[1] if len(sys.argv) > 1 else "examples/data"
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -58,7 +63,15 @@ def main():
     clouds["box2"] = a[:, :2].astype(np.float32)
     clouds["vtk0"] = load_vtk_points(os.path.join(REF, "cloud.00000.vtk")).astype(np.float32)
     clouds["vtk1"] = load_vtk_points(os.path.join(REF, "cloud.00001.vtk")).astype(np.float32)
+    vtk = {k: clouds.pop(k) for k in ("vtk0", "vtk1")}
     np.savez_compressed(os.path.join(OUT, "clouds.npz"), **clouds)
+    np.savez_compressed(os.path.join(OUT, "clouds_vtk.npz"), **vtk)
+    # the files themselves, for the loaders' test (tests/test_io.py)
+    os.makedirs(os.path.join(OUT, "data"), exist_ok=True)
+    shutil.copyfile(os.path.join(REF, "2D_oneBox.csv"), os.path.join(OUT, "data", "2D_oneBox.csv"))
+    for fn in ("car_cloud400.csv", "cloud.00000.vtk"):
+        with open(os.path.join(REF, fn), "rb") as src, open(os.path.join(OUT, "data", fn + ".gz"), "wb") as dst:
+            dst.write(gzip.compress(src.read(), 9, mtime=0))
 
     ref_trans = {}
     d = os.path.join(REF, "icp_data")

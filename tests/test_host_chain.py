@@ -51,9 +51,6 @@ def test_no_gpu_fails_loudly():
         icp.compute(pts, pts, np.ones((10, 3), np.float32))
 
 
-REF_DATA = "/root/reference/examples/data"
-
-
 def test_yaml_loads_reference_chain_files():
     from libpointmatcher_amd.icp import ICP
     icp = ICP(np.float32)

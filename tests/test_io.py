@@ -2,28 +2,34 @@
 reference IO.cpp:374-389, loadCSV :535-800, loadVTK :948-1252).  Host code:
 these tests run without a GPU.
 
-Pinned by the reference's own data files where they are present (the
-examples/data clouds the golden fixtures were extracted from: same values
-as tests/golden/clouds.npz) and by files written here in every layout the
+Pinned by the reference's own data files (tests/golden/data: the
+examples/data clouds the golden fixtures were extracted from, same values
+as tests/golden/clouds*.npz) and by files written here in every layout the
 loaders take: header / no header, the reference's delimiters, supported and
 unknown columns (the label table's order, spans grown by repeated names, a
 missing pad added), VTK ASCII and big-endian BINARY, POLYDATA cell blocks
 skipped, UNSTRUCTURED_GRID, SCALARS (LOOKUP_TABLE) / NORMALS / VECTORS /
 COLOR_SCALARS / FIELD arrays, and the reference's error messages.
 """
+import gzip
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 from libpointmatcher_amd.icp import load_cloud
 
-REF = "/root/reference/examples/data"
+DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "data")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present")
-def test_reference_files_match_golden(golden):
+def test_reference_files_match_golden(golden, tmp_path):
     g, _ = golden
+    REF = str(tmp_path)
+    shutil.copyfile(os.path.join(DATA, "2D_oneBox.csv"), os.path.join(REF, "2D_oneBox.csv"))
+    for fn in ("car_cloud400.csv", "cloud.00000.vtk"):  # (stored gzipped)
+        with gzip.open(os.path.join(DATA, fn + ".gz"), "rb") as src, open(os.path.join(REF, fn), "wb") as dst:
+            shutil.copyfileobj(src, dst)
     c = load_cloud(os.path.join(REF, "car_cloud400.csv"))
     assert c.feature_labels == [("x", 1), ("y", 1), ("z", 1), ("pad", 1)]
     assert c.descriptor_labels == [("normals", 3)]

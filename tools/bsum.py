@@ -1,10 +1,10 @@
-"""Summarise bench JSON lines in gpurun_out (dev tool)."""
+"""Summarise bench JSON lines (of bench.py --full runs) in a directory (dev tool)."""
 import glob
 import json
 import os
 import sys
 
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out"
+d = sys.argv[1] if len(sys.argv) > 1 else "bench_out"
 for f in sorted(glob.glob(os.path.join(d, "bench_*.json"))):
     try:
         j = json.load(open(f))

@@ -3,7 +3,7 @@
 usage: python tools/pmc_phases.py TRACE_DIR FETCH_DIR WRITE_DIR W K "COMMAND" > out.json
        (FETCH_DIR / WRITE_DIR may be "-": durations only)
 
-bench.py (with --no-cpu-baseline) ends, on the context stream (device loop,
+bench.py (with --full --no-cpu-baseline) ends, on the context stream (device loop,
 one ICP object), with pass A = prepare + W warmup + K timed iterations (the
 timed region) and pass B = prepare + W + K iterations with HIP events around
 every match (the live roofline measurement); nothing is dispatched after
