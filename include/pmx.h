@@ -22,6 +22,10 @@
  *   pmx_outlier_*       OutlierFilter::compute and the chain product
  *                         (PointMatcher.h:504-512, OutlierFilter.cpp:63-103,
  *                          OutlierFiltersImpl.cpp:51-223)
+ *   pmx_set_reading_normals / pmx_outlier_surface_normal
+ *                       SurfaceNormalOutlierFilter::compute on the step reading's
+ *                         rotated "normals" (OutlierFiltersImpl.cpp:225-285,
+ *                          ICP.cpp:381-390)
  *   pmx_p2plane_system  ErrorElements + PointToPlane normal equations
  *                         (ErrorMinimizer.cpp:58-193, PointToPlane.cpp:171-243)
  *   pmx_p2point_system  ErrorElements + PointToPoint weighted moments
@@ -170,6 +174,14 @@ int pmx_set_reading(pmx_ctx* ctx, const void* feat, int rows, int64_t N, const v
  * radii (squared in T, as libnabo does) instead of its maxDist.  Cleared by
  * the next pmx_set_reading. */
 int pmx_set_reading_radii(pmx_ctx* ctx, const void* radii);
+/* SurfaceNormalOutlierFilter: the reading's "normals" descriptor (D x N
+ * point-major T, in the order of pmx_set_reading's points; a sharded context
+ * takes its shard's; NULL clears).  The rotation block of pmx_set_reading's T0
+ * is applied once on the device (the reference transforms the descriptors
+ * with the points, ICP.cpp:345-347), each component (m0 n0 + m1 n1) + m2 n2
+ * in T, and the records follow the reading's slot order.  Cleared by the next
+ * pmx_set_reading. */
+int pmx_set_reading_normals(pmx_ctx* ctx, const void* normals);
 
 /* ------------------------------------------------------------- match --- */
 /* search structure, mirroring KDTreeMatcher's searchType
@@ -202,6 +214,15 @@ int pmx_outlier_mediandist(pmx_ctx* ctx, int chain_pos, double factor);
 int pmx_outlier_trimmed(pmx_ctx* ctx, int chain_pos, double ratio);
 int pmx_outlier_vartrimmed(pmx_ctx* ctx, int chain_pos, double minRatio, double maxRatio,
                            double lambda);
+/* SurfaceNormalOutlierFilter::compute (OutlierFiltersImpl.cpp:225-285) for
+ * the last pmx_match and its T_iter: eps = cos(maxAngle), computed by the
+ * caller in T.  w = 0 for an entry without neighbour, else 0 when
+ * |n^_reading . n^_reference| < eps with the reading normal rotated by T_iter
+ * and both normalised in T (a zero normal gives NaN and is kept), else 1.
+ * Without reading normals (pmx_set_reading_normals) or reference normals the
+ * filter is all ones, entries without neighbour included.  It reads no
+ * distance, so the quantile filters of the same chain are unaffected. */
+int pmx_outlier_surface_normal(pmx_ctx* ctx, int chain_pos, double eps);
 /* RobustOutlierFilter::robustFiltering (OutlierFiltersImpl.cpp:494-598):
  * real-valued weights w = robust(e^2), e^2 = dist / scale^2; at most one per
  * chain.  robust_fct: PMX_RF_*; tuning: k (after the berg substitution,
@@ -267,13 +288,15 @@ int pmx_sync(pmx_ctx* ctx);
  * Requirements: a grid matcher (pmx_set_search 1/2, per-lane kernel), filters
  * among default / Null / MaxDist / MinDist / MedianDist / TrimmedDist /
  * VarTrimmedDist / Robust (at most one; with PointToPoint only its
- * point2point distance), PointToPlane (no force2D / force4DOF) or
+ * point2point distance) / SurfaceNormal (at most one; filter_p[i][0] = eps
+ * = cos(maxAngle) in T), PointToPlane (no force2D / force4DOF) or
  * PointToPoint, checkers among Counter / Differential (smoothLength < 64) /
  * Bound.  Otherwise pmx_loop_begin returns PMX_E_BAD_PARAM and the caller
  * keeps the per-module calls. */
 enum { PMX_CHECK_COUNTER = 0, PMX_CHECK_DIFFERENTIAL = 1, PMX_CHECK_BOUND = 2 };
 enum { PMX_FILTER_DEFAULT = 0, PMX_FILTER_NULL = 1, PMX_FILTER_MAXDIST = 2, PMX_FILTER_MINDIST = 3,
-       PMX_FILTER_MEDIANDIST = 4, PMX_FILTER_TRIMMED = 5, PMX_FILTER_VARTRIMMED = 6, PMX_FILTER_ROBUST = 7 };
+       PMX_FILTER_MEDIANDIST = 4, PMX_FILTER_TRIMMED = 5, PMX_FILTER_VARTRIMMED = 6, PMX_FILTER_ROBUST = 7,
+       PMX_FILTER_SURFACENORMAL = 8 };
 /* RobustOutlierFilter's scale estimator in a loop configuration */
 enum { PMX_RSE_NONE = 0, PMX_RSE_MAD = 1, PMX_RSE_STD = 2, PMX_RSE_BERG = 3 };
 typedef struct pmx_loop_cfg {
@@ -281,7 +304,7 @@ typedef struct pmx_loop_cfg {
     double max_dist;
     int n_filters;              /* 0: the empty chain's default (dist != inf) */
     int filter_kind[8];         /* PMX_FILTER_* */
-    double filter_p[8][3];      /* maxDist / minDist / factor / ratio / (minRatio, maxRatio, lambda) */
+    double filter_p[8][3];      /* maxDist / minDist / factor / ratio / (minRatio, maxRatio, lambda) / eps */
     int minimizer;              /* 0 PointToPlane, 1 PointToPoint */
     int n_checkers;
     int checker_kind[8];        /* PMX_CHECK_* */

@@ -59,7 +59,8 @@ class Stats(C.Structure):
 
 # device-resident loop (pmx_loop_*)
 FILTER_KIND = {"default": 0, "NullOutlierFilter": 1, "MaxDistOutlierFilter": 2, "MinDistOutlierFilter": 3,
-               "MedianDistOutlierFilter": 4, "TrimmedDistOutlierFilter": 5, "VarTrimmedDistOutlierFilter": 6}
+               "MedianDistOutlierFilter": 4, "TrimmedDistOutlierFilter": 5, "VarTrimmedDistOutlierFilter": 6,
+               "SurfaceNormalOutlierFilter": 8}
 CHECK_KIND = {"CounterTransformationChecker": 0, "DifferentialTransformationChecker": 1,
               "BoundTransformationChecker": 2}
 
@@ -152,7 +153,7 @@ EXPORTS = [
     "pmx_comm_unique_id", "pmx_comm_init", "pmx_comm_init_host", "pmx_comm_size", "pmx_comm_stats", "pmx_comm_loop_stats", "pmx_set_reference", "pmx_set_reference_centred", "pmx_set_reference_mean_centred", "pmx_set_reading", "pmx_set_search", "pmx_match",
     "pmx_outlier_default", "pmx_outlier_null", "pmx_outlier_maxdist", "pmx_outlier_mindist",
     "pmx_outlier_mediandist", "pmx_outlier_trimmed", "pmx_outlier_vartrimmed", "pmx_outlier_robust",
-    "pmx_robust_scale", "pmx_set_reading_radii",
+    "pmx_robust_scale", "pmx_set_reading_radii", "pmx_set_reading_normals", "pmx_outlier_surface_normal",
     "pmx_p2plane_system", "pmx_p2point_system", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
@@ -195,6 +196,8 @@ def lib():
                                          C.c_int]
         l.pmx_robust_scale.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
         l.pmx_set_reading_radii.argtypes = [C.c_void_p, C.c_void_p]
+        l.pmx_set_reading_normals.argtypes = [C.c_void_p, C.c_void_p]
+        l.pmx_outlier_surface_normal.argtypes = [C.c_void_p, C.c_int, C.c_double]
         l.pmx_p2plane_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         l.pmx_p2point_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(Stats)]
@@ -445,6 +448,14 @@ class Context:
         r = self._arr(radii) if radii is not None else None
         self._chk(self._l.pmx_set_reading_radii(self.h, _ptr(r) if r is not None else None))
 
+    def set_reading_normals(self, normals):
+        """SurfaceNormalOutlierFilter: the reading's normals, N x D in the order of
+        set_reading's points (None clears; so does the next set_reading)."""
+        n = self._arr(normals) if normals is not None else None
+        if n is not None and n.shape != (self.N, self.rows - 1):
+            raise InvalidParameter(f"reading normals must be {self.N} x {self.rows - 1}, not {n.shape}")
+        self._chk(self._l.pmx_set_reading_normals(self.h, _ptr(n) if n is not None else None))
+
     # --- per-iteration
     def set_search(self, search_type: int):
         """0 = brute force, 1/2 = exact grid search (KDTreeMatcher searchType)."""
@@ -478,6 +489,13 @@ class Context:
         else:
             raise InvalidParameter(f"unknown outlier filter {name}")
         self._chk(rc)
+
+    def outlier_surface_normal(self, pos=0, eps=None, max_angle=1.57):
+        """SurfaceNormalOutlierFilter: eps = cos(maxAngle) in the context's dtype
+        (computed here from max_angle unless given)."""
+        if eps is None:
+            eps = np.cos(self.dtype.type(max_angle))
+        self._chk(self._l.pmx_outlier_surface_normal(self.h, pos, float(eps)))
 
     def outlier_robust(self, pos=0, fct="cauchy", tuning=1.0, approximation=np.inf, scale_mode=RS_MAD,
                        berg_target=0.0, point2plane=False):

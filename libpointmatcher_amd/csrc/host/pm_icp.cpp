@@ -420,6 +420,31 @@ struct RobustOF : PM<T>::OutlierFilter {
     void loopAdvance(int64_t iterations) override { iteration += (int)iterations; }
 };
 
+// SurfaceNormalOutlierFilter (OutlierFiltersImpl.h:176-194,
+// OutlierFiltersImpl.cpp:225-285): eps = cos(maxAngle) in T, here; the
+// weights on the device from the reading's resident normals
+// (ICP::uploadReadingNormals) and the matched reference normals.
+template <typename T>
+struct SurfaceNormalOF : PM<T>::OutlierFilter {
+    T eps;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("maxAngle", "largest angle allowed between the two surface normals (radian)", "1.57", "0.0",
+                     "3.1416", &Parametrizable::Comp<T>)};
+    }
+    explicit SurfaceNormalOF(const Parametrizable::Parameters& p)
+        : PM<T>::OutlierFilter("SurfaceNormalOutlierFilter", doc(), p),
+          eps(std::cos(this->template get<T>("maxAngle"))) {}
+    bool needsReadingNormals() const override { return true; }
+    void compute(Device& d, const typename PM<T>::Matches&, int pos) override {
+        d.check(pmx_outlier_surface_normal(d.ctx, pos, (double)eps));
+    }
+    bool loopConfig(pmx_loop_cfg& cfg, int pos) const override {
+        cfg.filter_kind[pos] = PMX_FILTER_SURFACENORMAL;
+        cfg.filter_p[pos][0] = (double)eps;
+        return true;
+    }
+};
+
 // ---- error minimisers -----------------------------------------------------
 template <typename T>
 void build_p2plane_transform(int rows, const T* x, std::vector<T>& out) {
@@ -1160,6 +1185,8 @@ PointMatcher<T>::PointMatcher() {
                                [](const Ps& p) { return std::make_shared<VarTrimmedDistOF<T>>(p); }, true);
     OutlierFilterRegistrar.reg("RobustOutlierFilter", [](const Ps& p) { return std::make_shared<RobustOF<T>>(p); },
                                true);
+    OutlierFilterRegistrar.reg("SurfaceNormalOutlierFilter",
+                               [](const Ps& p) { return std::make_shared<SurfaceNormalOF<T>>(p); }, true);
     ErrorMinimizerRegistrar.reg("PointToPlaneErrorMinimizer",
                                 [](const Ps& p) { return std::make_shared<PointToPlaneEM<T>>(p); }, true);
     ErrorMinimizerRegistrar.reg("PointToPointErrorMinimizer",
@@ -1415,6 +1442,7 @@ void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const Tra
     // transformations.apply(reading, T_refMean_dataIn): done on the device
     dev.check(pmx_set_reading(dev.ctx, reading.feat(), dim, reading.n, T_refMean_dataIn_.data()));
     matcher->initReading(dev, reading);  // (per-reading matcher inputs: KDTreeVarDistMatcher's radii)
+    uploadReadingNormals(reading);       // (SurfaceNormalOutlierFilter; rotated by T_refMean_dataIn on the device)
     // readingStepDataPointsFilters (ICP.cpp:349-350, 373-377): the step
     // filters see the reading in <refMean> every iteration; keep that copy on
     // the host (the device's transform, restated: the same separately rounded
@@ -1433,6 +1461,28 @@ void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const Tra
                 v = v + (D == 3 ? m[2] * f[2] : (T)0 * (T)0);
                 v = v + m[D] * f[D];
                 o[r] = v;
+            }
+        }
+        // (its normals as the reference's transformation leaves them: the
+        // rotation block applied in T, the same terms as the device's upload)
+        bool wantNormals = false;
+        for (auto& f : outlierFilters) wantNormals = wantNormals || f->needsReadingNormals();
+        if (wantNormals && stepBase_.descriptorExists("normals")) {
+            int span = 0;
+            std::vector<T> nr = stepBase_.descriptor("normals", &span);
+            if (span == D) {
+                const T* m = T_refMean_dataIn_.data();
+                for (int64_t j = 0; j < stepBase_.n; ++j) {
+                    T* v = &nr[(size_t)j * D];
+                    T o[3] = {0, 0, 0};
+                    for (int r = 0; r < D; ++r) {
+                        T s = m[r * dim + 0] * v[0] + m[r * dim + 1] * v[1];
+                        if (D == 3) s = s + m[r * dim + 2] * v[2];
+                        o[r] = s;
+                    }
+                    for (int r = 0; r < D; ++r) v[r] = o[r];
+                }
+                stepBase_.setDescriptor("normals", span, nr.data());
             }
         }
         for (auto& f : readingStepDataPointsFilters) f->device = dev.device;
@@ -1570,6 +1620,19 @@ bool PointMatcher<T>::ICP::step() {
     return iterate(1);
 }
 
+template <typename T>
+void PointMatcher<T>::ICP::uploadReadingNormals(const DataPoints& reading) {
+    bool want = false;
+    for (auto& f : outlierFilters) want = want || f->needsReadingNormals();
+    if (!want || !reading.descriptorExists("normals")) return;  // (pmx_set_reading cleared the last reading's)
+    int span = 0;
+    const std::vector<T> nr = reading.descriptor("normals", &span);
+    if (span != reading.rows - 1)
+        throw InvalidElement("SurfaceNormalOutlierFilter: descriptor normals must have " +
+                             std::to_string(reading.rows - 1) + " rows, not " + std::to_string(span));
+    dev.check(pmx_set_reading_normals(dev.ctx, nr.data()));
+}
+
 // every module's device form, or false (ICP.cpp:371-430 then runs through the
 // module calls)
 template <typename T>
@@ -1651,6 +1714,7 @@ bool PointMatcher<T>::ICP::stepModules() {
         for (int i = 0; i < dim; ++i) I[(size_t)i * dim + i] = 1;
         dev.check(pmx_set_reading(dev.ctx, stepReading.features.data(), dim, stepReading.n, I.data()));
         matcher->initReading(dev, stepReading);
+        uploadReadingNormals(stepReading);
     }
     const Matches matches = matcher->findClosests(dev, T_iter_);
     outlierFilters.compute(dev, matches);

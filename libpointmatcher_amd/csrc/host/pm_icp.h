@@ -98,6 +98,9 @@ struct PointMatcher {
         // the device loop ran `iterations` more calls of this filter (its
         // per-call state, as the per-module calls would have left it)
         virtual void loopAdvance(int64_t /*iterations*/) {}
+        // the filter reads the reading's "normals" descriptor on the device
+        // (SurfaceNormalOutlierFilter): the ICP uploads it with the reading
+        virtual bool needsReadingNormals() const { return false; }
     };
     struct OutlierFilters : std::vector<std::shared_ptr<OutlierFilter>> {
         void compute(Device& dev, const Matches& m);  // OutlierFilter.cpp:63-103
@@ -247,6 +250,9 @@ struct PointMatcher {
         bool stepModules();                   // ICP.cpp:371-430 through the module calls
         bool loopConfig(pmx_loop_cfg& cfg) const;
         void prepareReading(const DataPoints& readingIn, const TransformationParameters& T_init);
+        // the reading's "normals" to the device when a filter of the chain
+        // reads them (after every reading upload)
+        void uploadReadingNormals(const DataPoints& reading);
         DataPoints stepBase_;                 // the reading in <refMean> (readingStepDataPointsFilters)
         DataPoints map_;                      // the map in <refMean>, filtered (mapPointCloud)
         TransformationParameters T_map_;      // its T_refIn_refMean

@@ -577,6 +577,8 @@ int set_reading_impl(pmx_ctx* c, const T* feat, int rows, int64_t N, const T* T0
     const int64_t n1 = std::max<int64_t>(N, 1);
     SetupTrace tr(c);
     c->has_radii = false;  // (a new reading: its radii, if any, follow)
+    c->has_rnrm = false;   // (and its normals, pmx_set_reading_normals)
+    for (int i = 0; i < 16; ++i) c->T0[i] = (double)M0.m[i];
     // raw P4 reading (pack), then the slot order, then T_refMean_dataIn
     // (scratch and the resident reading kept across readings: ICPSequence
     // scans pay no allocation)
@@ -1093,6 +1095,20 @@ WChain<T> chain_of(const pmx_ctx* c) {
         w.rb_scale = c->rob_scale(c->rb_pos);
         w.rb_p2pl = c->rb_p2pl;
     }
+    // SurfaceNormalOutlierFilter: all ones unless both clouds carry normals
+    // (OutlierFiltersImpl.cpp:247); several of them reject what the largest
+    // eps rejects
+    if (c->has_rnrm && c->has_normals) {
+        for (int i = 0; i < c->chain_n; ++i) {
+            if (c->chain_type[i] != kWPNormal) continue;
+            const T eps = (T)c->chain_thr[i];
+            w.sn.eps = w.sn.rn && !(eps > w.sn.eps) ? w.sn.eps : eps;
+            w.sn.rn = (const P4<T>*)c->d_rnrm_p4;
+            w.sn.nrm = (const P4<T>*)match_nrm(c);
+            w.sn.rs = match_rs(c);
+            w.sn.dim = c->dim;
+        }
+    }
     return w;
 }
 
@@ -1201,6 +1217,9 @@ int outlier_impl(pmx_ctx* c, int kind, int chain_pos, double p0, double p1, doub
         chain_set(c, chain_pos, kWPState, 1.0);
         break;
     }
+    case 8:  // SurfaceNormal: p0 = eps = cos(maxAngle) in T; reads no distance (pmx_snormal.h)
+        chain_set(c, chain_pos, kWPNormal, (double)(T)p0);
+        break;
     default:
         return fail(c, PMX_E_BAD_PARAM, "unknown outlier filter");
     }
@@ -1296,6 +1315,35 @@ int set_radii_impl(pmx_ctx* c, const T* radii) {
     return PMX_OK;
 }
 
+// SurfaceNormalOutlierFilter: the reading's "normals" descriptor as resident
+// records, in the slot order of the reading and rotated by T0's rotation
+// block (what transformations.apply leaves in the reading, ICP.cpp:345-347)
+template <typename T>
+int set_reading_normals_impl(pmx_ctx* c, const T* normals) {
+    c->w_valid = false;
+    if (!normals) {
+        c->has_rnrm = false;
+        return PMX_OK;
+    }
+    if (!c->d_rd && c->N > 0) return fail(c, PMX_E_STATE, "pmx_set_reading must be called first");
+    const int64_t n1 = std::max<int64_t>(c->N, 1);
+    const size_t raw_bytes = (sizeof(T) * (size_t)c->dim * (size_t)n1 + 255) & ~(size_t)255;
+    int rc;
+    if ((rc = ensure(c, &c->d_rnrm, &c->rnrm_bytes, raw_bytes + sizeof(P4<T>) * (size_t)n1))) return rc;
+    P4<T>* rec = (P4<T>*)((char*)c->d_rnrm + raw_bytes);  // (upload part, then the records)
+    HIPCHK(c, hipMemcpyAsync(c->d_rnrm, normals, sizeof(T) * (size_t)c->dim * (size_t)c->N, hipMemcpyHostToDevice,
+                             c->stream));
+    Mat4<T> M0{};
+    for (int i = 0; i < 16; ++i) M0.m[i] = (T)c->T0[i];
+    launch_reading_normals<T>((const T*)c->d_rnrm, c->dim, c->has_order ? c->d_order : nullptr, c->N, M0, rec,
+                              c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's buffer may go)
+    c->d_rnrm_p4 = rec;
+    c->has_rnrm = true;
+    return PMX_OK;
+}
+
 template <typename T>
 int robust_scale_impl(pmx_ctx* c, int pos, double* scale) {
     if (pos < 0 || pos >= kMaxChain || !c->d_rob) return fail(c, PMX_E_STATE, "no RobustOutlierFilter scale at this position");
@@ -1318,6 +1366,26 @@ int select_reset(pmx_ctx* c) {
 // one D2H copy of the iteration block, then a stream sync
 int readback(pmx_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(c->h_result, c->d_result, kBlkCopy, hipMemcpyDeviceToHost, c->stream));
+    // A chain with the SurfaceNormalOutlierFilter reports the threshold of its
+    // last quantile filter wherever that stands: the normal filter reads no
+    // distance, so [SurfaceNormal, Trimmed] and [Trimmed, SurfaceNormal] must
+    // report the same limit.  Only such chains: every other chain keeps
+    // reporting position 0's select state, as it always has (callers may read
+    // that diagnostic), and issues no copy beyond the iteration block.  The
+    // select state of a later position lies outside the iteration block, so
+    // its limit takes one more small copy, into the pinned h_result's tail:
+    // the 8 bytes at kBlkCopy, past everything the block copy writes
+    // (h_result is kBlkBytes long; module_limit reads them back).
+    c->limit_pos = 0;
+    bool sn = false;
+    for (int i = 0; i < c->chain_n; ++i) {
+        sn = sn || c->chain_type[i] == kWPNormal;
+        if (c->chain_type[i] == kWPState) c->limit_pos = i;
+    }
+    if (!sn) c->limit_pos = 0;
+    if (c->limit_pos > 0)
+        HIPCHK(c, hipMemcpyAsync((char*)c->h_result + kBlkCopy, &c->sel_slot(c->limit_pos)->limit, sizeof(double),
+                                 hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_events(c);
     return PMX_OK;
@@ -1326,6 +1394,13 @@ int host_iter_err(const pmx_ctx* c) {
     int e = 0;
     std::memcpy(&e, (const char*)c->h_result + kBlkIterErr, sizeof(int));
     return e;
+}
+// (module path, after readback)
+double module_limit(const pmx_ctx* c) {
+    if (c->limit_pos <= 0) return host_limit(c);
+    double v = 0;
+    std::memcpy(&v, (const char*)c->h_result + kBlkCopy, sizeof(double));
+    return v;
 }
 double host_limit(const pmx_ctx* c) {
     double v = 0;
@@ -1359,14 +1434,23 @@ void after_readback(pmx_ctx* c) {
     choose_level(c, v, f);
 }
 
+// k = 1 after a grid match that left its neighbour records with the normals
+// (d_nbr: points, then normals, in slot order)
+bool nbr_with_normals(const pmx_ctx* c) { return c->nbr_prev && c->nbr_normals && c->knn == 1 && c->ids_grid; }
+
 // the chain's weights into d_w (the host mirror; a point-to-plane robust
 // distance under the point-to-point minimiser)
 template <typename T>
 int materialise_weights(pmx_ctx* c) {
     if (c->w_valid) return PMX_OK;
-    launch_weights_chain<T>((const T*)c->d_dists, (T*)c->d_w, c->N * c->knn, chain_of<T>(c), (const P4<T>*)c->d_rd,
-                            step_mat<T>(c), (const P4<T>*)match_pn(c), (const P4<T>*)match_nrm(c), match_rs(c),
-                            c->d_ids, c->knn, c->stream);
+    const WChain<T> chain = chain_of<T>(c);
+    const Mat4<T> Tm = step_mat<T>(c);
+    launch_weights_chain<T>((const T*)c->d_dists, (T*)c->d_w, c->N * c->knn, chain, (const P4<T>*)c->d_rd, Tm,
+                            (const P4<T>*)match_pn(c), (const P4<T>*)match_nrm(c), match_rs(c), c->d_ids, c->knn,
+                            c->stream);
+    if (chain.sn.rn)  // the SurfaceNormalOutlierFilter's factor (pmx_snormal.hip)
+        launch_sn_weights<T>((T*)c->d_w, c->N * c->knn, c->knn, chain.sn, Tm, c->d_ids,
+                             nbr_with_normals(c) ? (const P4<T>*)c->d_nbr + c->N : nullptr, c->stream);
     HIPCHK(c, hipGetLastError());
     c->w_valid = true;
     return PMX_OK;
@@ -1380,7 +1464,7 @@ int p2plane_enqueue(pmx_ctx* c) {
     Mat4<T> Tm = step_mat<T>(c);
     // (k = 1 after a match that left its neighbour records with normals:
     // the reduction reads them in slot order instead of gathering by id)
-    const bool nbr = c->nbr_prev && c->nbr_normals && c->knn == 1 && c->ids_grid && !chain.robust;
+    const bool nbr = nbr_with_normals(c) && !chain.robust;
     launch_p2plane_partial<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_pn(c), (const P4<T>*)match_nrm(c),
                               match_rs(c), (const T*)c->d_dists, c->d_ids, chain, c->knn, c->N, c->dim, c->d_partials,
                               loop_ctl(c), (const GridDesc<T>*)c->d_gdesc, c->vpart_dirty ? c->d_vpart : nullptr,
@@ -1457,7 +1541,7 @@ int p2plane_impl(pmx_ctx* c, double* A, double* b, pmx_stats* st) {
     const double* r = c->h_result;
     const int ierr = host_iter_err(c);
     const int o = NS + NF;
-    fill_stats(c, st, r[o + 0], r[o + 1], r[o + 2], r[o + 3], r[o + 4], host_limit(c));
+    fill_stats(c, st, r[o + 0], r[o + 1], r[o + 2], r[o + 3], r[o + 4], module_limit(c));
     if (ierr == PMX_E_EMPTY_QUANTILE) return fail(c, PMX_E_EMPTY_QUANTILE, "no outlier to filter");
     if (ierr == kSelTimeout) {
         (void)select_reset(c);
@@ -1486,7 +1570,7 @@ int p2point_impl(pmx_ctx* c, double* mean_p, double* mean_q, double* m, pmx_stat
     after_readback(c);
     const double* r = c->h_result;
     const int ierr = host_iter_err(c);
-    fill_stats(c, st, r[7], r[8], r[9], r[10], r[0], host_limit(c));
+    fill_stats(c, st, r[7], r[8], r[9], r[10], r[0], module_limit(c));
     if (ierr == PMX_E_EMPTY_QUANTILE) return fail(c, PMX_E_EMPTY_QUANTILE, "no outlier to filter");
     if (ierr == kSelTimeout) {
         (void)select_reset(c);
@@ -1617,6 +1701,13 @@ int pmx_set_reading_radii(pmx_ctx* c, const void* radii) {
     return DISPATCH(c, set_radii_impl<float>(c, (const float*)radii), set_radii_impl<double>(c, (const double*)radii));
 }
 
+int pmx_set_reading_normals(pmx_ctx* c, const void* normals) {
+    if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c, set_reading_normals_impl<float>(c, (const float*)normals),
+                    set_reading_normals_impl<double>(c, (const double*)normals));
+}
+
 int pmx_match(pmx_ctx* c, const void* T_iter, int knn, double maxDist, double epsilon, uint64_t* visited) {
     if (!c || !T_iter) return fail(c, PMX_E_BAD_PARAM, "null argument");
     if (!(epsilon >= 0)) return fail(c, PMX_E_BAD_PARAM, "epsilon must be >= 0");
@@ -1635,6 +1726,7 @@ int pmx_outlier_mindist(pmx_ctx* c, int pos, double m) { return OUTLIER(c, 3, po
 int pmx_outlier_mediandist(pmx_ctx* c, int pos, double f) { return OUTLIER(c, 4, pos, f, 0, 0); }
 int pmx_outlier_trimmed(pmx_ctx* c, int pos, double r) { return OUTLIER(c, 5, pos, r, 0, 0); }
 int pmx_outlier_vartrimmed(pmx_ctx* c, int pos, double a, double b, double l) { return OUTLIER(c, 6, pos, a, b, l); }
+int pmx_outlier_surface_normal(pmx_ctx* c, int pos, double eps) { return OUTLIER(c, 8, pos, eps, 0, 0); }
 
 int pmx_p2plane_system(pmx_ctx* c, double* A, double* b, pmx_stats* st) {
     if (!c || !A || !b) return fail(c, PMX_E_BAD_PARAM, "null argument");

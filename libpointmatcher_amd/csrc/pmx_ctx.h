@@ -190,6 +190,14 @@ struct pmx_ctx {
     void* d_radii = nullptr;
     size_t radii_bytes = 0;
     bool has_radii = false;
+    // SurfaceNormalOutlierFilter: the reading's normals, rotated by T0's
+    // rotation block, in slot order (pmx_set_reading_normals): the upload
+    // half, then P4<T>[N]
+    double T0[16] = {0};  // pmx_set_reading's T0 (embedded 4x4, T values)
+    void* d_rnrm = nullptr;
+    size_t rnrm_bytes = 0;
+    const void* d_rnrm_p4 = nullptr;  // (the records, inside d_rnrm)
+    bool has_rnrm = false;
 
     // matches / weights
     int knn = 0;
@@ -209,6 +217,7 @@ struct pmx_ctx {
     int chain_type[kMaxChain] = {};
     double chain_thr[kMaxChain] = {};
     bool w_valid = false;  // d_w holds the chain's weights (mirror only)
+    int limit_pos = 0;     // chain position whose quantile the last readback reports (readback)
     // RobustOutlierFilter (at most one per chain): its parameters, and the
     // device block of its scale state: SelectState (the MAD's second
     // select), then the scale of each chain position, then the moment sums

@@ -317,7 +317,21 @@ void launch_pos_to_index(const int32_t* pos, const int32_t* gidx, int32_t* out, 
 // filter with real-valued weights: w = robust(e^2), e^2 = dist / scale^2,
 // multiplied with the predicates' 0/1 (kWPRobust, at most one per chain; the
 // reductions take the weighted path only then).
-enum WPred { kWPDefault = 0, kWPNull = 1, kWPLe = 2, kWPGe = 3, kWPState = 4, kWPRobust = 5 };
+// The SurfaceNormalOutlierFilter (OutlierFiltersImpl.cpp:225-285) is the one
+// predicate that reads no distance (kWPNormal): it compares the reading's and
+// the matched reference point's normals (SNPred, pmx_snormal.h).  The
+// reductions evaluate it in instantiations of their own, selected at launch
+// when the chain holds it.
+enum WPred { kWPDefault = 0, kWPNull = 1, kWPLe = 2, kWPGe = 3, kWPState = 4, kWPRobust = 5, kWPNormal = 6 };
+// rn != null: the filter is in the chain and both clouds carry normals.
+template <typename T>
+struct SNPred {
+    const P4<T>* rn = nullptr;   // [N]: the reading's normals, rotated by T_refMean_dataIn, slot order
+    const P4<T>* nrm = nullptr;  // the reference normal records the match ids index (device loop: from GridDesc)
+    int rs = 1;                 // their index stride (2: a grid level's interleaved records)
+    int dim = 3;
+    T eps = 0;                  // cos(maxAngle) in T (several filters: the largest)
+};
 enum RobustFct { kRFCauchy = 0, kRFWelsch = 1, kRFSC = 2, kRFGM = 3, kRFTukey = 4, kRFHuber = 5, kRFL1 = 6,
                  kRFStudent = 7 };
 constexpr int kMaxChain = 8;
@@ -336,6 +350,7 @@ struct WChain {
     const double* rb_scale = nullptr;
     int rb_p2pl = 0;
     const T* w_arr = nullptr;  // materialised weights (a robust point-to-plane distance, point-to-point minimiser)
+    SNPred<T> sn;              // kWPNormal
 };
 // robustFiltering's weight of one scaled squared error (OutlierFiltersImpl.cpp:541-596)
 template <typename T>
@@ -408,6 +423,18 @@ template <typename T>
 __device__ __forceinline__ bool chain_keep(const WRange<T>& r, T d) {
     return (!r.finite || d != (T)__builtin_huge_val()) && d >= r.lo && d <= r.hi;
 }
+
+// ---- SurfaceNormalOutlierFilter (pmx_snormal.hip) ----
+// the reading's normals (raw: D x n point-major) as resident records in slot
+// order (order == null: identity), rotated by the rotation block of M0
+template <typename T>
+void launch_reading_normals(const T* raw, int D, const int32_t* order, int64_t n, const Mat4<T>& M0, P4<T>* out,
+                            hipStream_t s);
+// w[e] *= the filter's 0/1 (the materialised weights, n = N * k entries);
+// nbr_n (may be null): the k = 1 neighbour records' normals, in slot order
+template <typename T>
+void launch_sn_weights(T* w, int64_t n, int k, const SNPred<T>& p, const Mat4<T>& Tm, const int32_t* ids,
+                       const P4<T>* nbr_n, hipStream_t s);
 
 // ---- robust scale estimators (pmx_robust.hip) ----
 // the exact median index count / 2 (Matches::getMedianAbsDeviation's

@@ -37,12 +37,13 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg, const T* T0) {
     if (!(cfg->max_dist >= 0)) return fail(c, PMX_E_BAD_PARAM, "maxDist must be >= 0");
     if (cfg->n_filters < 0 || cfg->n_filters > kMaxChain)
         return fail(c, PMX_E_BAD_PARAM, "device loop: at most 8 outlier filters");
-    int n_robust = 0;
+    int n_robust = 0, n_normal = 0;
     for (int i = 0; i < cfg->n_filters; ++i) {
         const int k = cfg->filter_kind[i];
         const double* p = cfg->filter_p[i];
-        if (k < PMX_FILTER_DEFAULT || k > PMX_FILTER_ROBUST || (k == PMX_FILTER_DEFAULT && i != 0))
+        if (k < PMX_FILTER_DEFAULT || k > PMX_FILTER_SURFACENORMAL || (k == PMX_FILTER_DEFAULT && i != 0))
             return fail(c, PMX_E_BAD_PARAM, "device loop: unknown outlier filter");
+        if (k == PMX_FILTER_SURFACENORMAL) ++n_normal;
         if (k == PMX_FILTER_ROBUST) {
             ++n_robust;
             if (cfg->robust_fct < PMX_RF_CAUCHY || cfg->robust_fct > PMX_RF_STUDENT ||
@@ -61,6 +62,7 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg, const T* T0) {
             return fail(c, PMX_E_BAD_PARAM, "VarTrimmedDistOutlierFilter: minRatio should be smaller than maxRatio");
     }
     if (n_robust > 1) return fail(c, PMX_E_BAD_PARAM, "device loop: one RobustOutlierFilter per chain");
+    if (n_normal > 1) return fail(c, PMX_E_BAD_PARAM, "device loop: one SurfaceNormalOutlierFilter per chain");
     if (cfg->minimizer != 0 && cfg->minimizer != 1) return fail(c, PMX_E_BAD_PARAM, "device loop: unknown minimizer");
     if (cfg->minimizer == 0 && !c->has_normals)
         return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer requires \"normals\" on the reference");

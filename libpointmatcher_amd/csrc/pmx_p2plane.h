@@ -3,6 +3,7 @@
 #pragma once
 
 #include "pmx_internal.h"
+#include "pmx_snormal.h"
 
 namespace pmx {
 
@@ -126,7 +127,11 @@ __device__ __forceinline__ void p2plane_add(double (&acc)[NV], T px, T py, T pz,
 // one block's sums to partials[v * gridDim.x + blockIdx.x]
 // k up to this: the reduction issues a query's k gathers together
 constexpr int kGatherK = 4;
-template <typename T, int DIM, bool kCoherent = false>
+// SN: the chain holds the SurfaceNormalOutlierFilter (chain.sn, pmx_snormal.h):
+// every entry's id and the reading's normal are loaded as well, the gathered
+// reference normal serves both the predicate and F, and a pair counts as kept
+// only when both predicates pass (the product of the weights)
+template <typename T, int DIM, bool kCoherent = false, bool SN = false>
 __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const Mat4<T>& Tm,
                                              const P4<T>* __restrict__ ref, const P4<T>* __restrict__ nrm, int rs,
                                              const T* __restrict__ d, const int32_t* __restrict__ ids,
@@ -156,6 +161,7 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
             T dv[U];
             int32_t id[U];
             P4<T> q[U], n[U];
+            P4<T> rn[SN ? U : 1];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t ii = i0 + u * stride;
@@ -165,16 +171,20 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
                 if (nbr) {
                     q[u] = nbr[jj];
                     n[u] = nbr[N + jj];
+                    if (SN) id[u] = ids[jj];
                 } else {
                     id[u] = ids[jj];
                 }
+                if (SN) rn[u] = gld(chain.sn.rn, jj);
             }
             bool kp[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 kp[u] = i0 + u * stride < N && dv[u] != inf && chain_keep(wr, dv[u]);
                 if (!nbr) {
-                    const int64_t g = (int64_t)(kp[u] ? id[u] : 0) * rs;  // (position 0 always exists)
+                    // (SN: the normal of every valid entry the distances keep, also at an infinite distance)
+                    const bool gat = SN ? i0 + u * stride < N && id[u] >= 0 && chain_keep(wr, dv[u]) : kp[u];
+                    const int64_t g = (int64_t)(gat ? id[u] : 0) * rs;  // (position 0 always exists)
                     q[u] = gld(ref, g);
                     n[u] = gld(nrm, g);
                 }
@@ -182,7 +192,11 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (i0 + u * stride >= N) continue;
-                const bool keep = chain_keep(wr, dv[u]);
+                bool keep = chain_keep(wr, dv[u]);
+                if (SN) {
+                    keep = keep && id[u] >= 0 && sn_pass(chain.sn, Tm, rn[u], n[u]);
+                    kp[u] = kp[u] && keep;
+                }
                 if (keep) acc[NS + NF + 1] += 1.0;                 // (w != 0).count()
                 if (dv[u] != inf && !keep) acc[NS + NF + 2] += 1.0;  // rejected match
                 if (!kp[u]) {
@@ -215,18 +229,22 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
             P4<T> q[kGatherK], n[kGatherK];
 #pragma unroll
             for (int s = 0; s < kGatherK; ++s) {
-                const bool kp = s < k && dv[s] != inf && chain_keep(wr, dv[s]);
+                const bool kp = SN ? s < k && id[s] >= 0 && chain_keep(wr, dv[s])
+                                   : s < k && dv[s] != inf && chain_keep(wr, dv[s]);
                 const int64_t g = (int64_t)(kp ? id[s] : 0) * rs;  // (position 0 always exists)
                 q[s] = gld(ref, g);
                 n[s] = gld(nrm, g);
             }
             T px, py, pz;
             xform3(Tm, rp, px, py, pz);
+            P4<T> rn{};
+            if (SN) rn = gld(chain.sn.rn, i);
             bool exist = false;
 #pragma unroll
             for (int s = 0; s < kGatherK; ++s) {
                 if (s >= k) continue;
-                const bool keep = chain_keep(wr, dv[s]);
+                bool keep = chain_keep(wr, dv[s]);
+                if (SN) keep = keep && id[s] >= 0 && sn_pass(chain.sn, Tm, rn, n[s]);
                 if (keep) acc[NS + NF + 1] += 1.0;  // (w != 0).count()
                 if (dv[s] == inf) continue;
                 if (!keep) {
@@ -248,7 +266,11 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
             const T dv = d[e];
-            const bool keep = chain_keep(wr,dv);
+            bool keep = chain_keep(wr,dv);
+            if (SN) {
+                const int32_t id = ids[e];
+                keep = keep && id >= 0 && sn_pass(chain.sn, Tm, gld(chain.sn.rn, i), gld(nrm, (int64_t)id * rs));
+            }
             if (keep) acc[NS + NF + 1] += 1.0;  // (w != 0).count()
             if (dv == inf) continue;
             if (!keep) {

@@ -47,9 +47,22 @@ __device__ __forceinline__ T p2pl_distance(T px, T py, T pz, const P4<T>& q, con
     return dot * dot;  // (pow(dot, 2) rounds to the same T)
 }
 
+// The chain's weight of entry e (slot i) in the point-to-point reductions.
+// SN (the chain holds the SurfaceNormalOutlierFilter): times the filter's 0/1,
+// which gathers the matched reference normal (these kernels carry none
+// otherwise); materialised weights (w_arr) hold the factor already.
+template <typename T, bool SN>
+__device__ __forceinline__ T pair_weight(const WChain<T>& chain, const SNPred<T>& sn, const WRange<T>& wr,
+                                         const Mat4<T>& Tm, T dv, int64_t i, int64_t e,
+                                         const int32_t* __restrict__ ids) {
+    T w = chain.robust ? robust_chain_weight(chain, wr, dv, e) : (chain_keep(wr, dv) ? (T)1 : (T)0);
+    if (SN && !chain.w_arr && w != (T)0) w = w * (sn_entry(sn, Tm, i, ids[e]) ? (T)1 : (T)0);
+    return w;
+}
+
 // result layout: [0, NS) upper triangle of A row-major (r <= c), [NS, NS+NF) b,
 // then kept, nonzero weights, rejected matches, rejected points
-template <typename T, int DIM>
+template <typename T, int DIM, bool SN>
 __global__ __launch_bounds__(256) void p2plane_partial_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                               const P4<T>* __restrict__ ref,
                                                               const P4<T>* __restrict__ nrm, int rs,
@@ -69,7 +82,7 @@ __global__ __launch_bounds__(256) void p2plane_partial_kernel(const P4<T>* __res
     }
     if (vzero && blockIdx.x == 0)  // (the spread counters the merged counter phase read, for the next match)
         for (int c = 0; c < 4; ++c) vzero[(size_t)(c * kVSlots + threadIdx.x) * kVStride] = 0ull;
-    p2plane_body<T, DIM>(rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, nbr);
+    p2plane_body<T, DIM, false, SN>(rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, nbr);
 }
 
 // Real-valued weights (a RobustOutlierFilter in the chain; per-module path):
@@ -104,7 +117,7 @@ __device__ __forceinline__ void p2plane_add_full(double (&acc)[NV], T px, T py, 
         acc[NF * NF + r] += (double)(wF * dot);
     }
 }
-template <typename T, int DIM>
+template <typename T, int DIM, bool SN>
 __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                                const P4<T>* __restrict__ ref,
                                                                const P4<T>* __restrict__ nrm, int rs,
@@ -146,7 +159,8 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
             // (the predicates judge the match distance; the robust function the chosen one)
             const T pred = chain_keep(wr, dv) ? (T)1 : (T)0;
             const T sc = (T)*chain.rb_scale;
-            const T w = pred * robust_weight<T>(chain.rb_fct, chain.rb_k, chain.rb_sqa, dist / (sc * sc));
+            T w = pred * robust_weight<T>(chain.rb_fct, chain.rb_k, chain.rb_sqa, dist / (sc * sc));
+            if (SN) w = w * (id >= 0 && sn_pass(chain.sn, Tm, gld(chain.sn.rn, i), n) ? (T)1 : (T)0);
             if (w != (T)0) acc[NS + NF + 1] += 1.0;  // (w != 0).count()
             if (dv == inf) continue;
             if (w == (T)0) {
@@ -168,21 +182,18 @@ void launch_p2plane_partial(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref
                             const T* d, const int32_t* ids, const WChain<T>& chain, int k, int64_t N, int dim,
                             double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, unsigned long long* vzero,
                             hipStream_t s, const P4<T>* nbr) {
+    const bool sn = chain.sn.rn != nullptr;  // (the instantiations with the normal predicate)
     if (chain.robust) {  // real-valued weights: the full asymmetric A
-        if (dim == 3)
-            hipLaunchKernelGGL((p2plane_weighted_kernel<T, 3>), dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm,
-                               rs, d, ids, chain, k, N, partials, ctl, gd);
-        else
-            hipLaunchKernelGGL((p2plane_weighted_kernel<T, 2>), dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm,
-                               rs, d, ids, chain, k, N, partials, ctl, gd);
+        auto* const kern = dim == 3 ? (sn ? p2plane_weighted_kernel<T, 3, true> : p2plane_weighted_kernel<T, 3, false>)
+                                    : (sn ? p2plane_weighted_kernel<T, 2, true> : p2plane_weighted_kernel<T, 2, false>);
+        hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials,
+                           ctl, gd);
         return;
     }
-    if (dim == 3)
-        hipLaunchKernelGGL((p2plane_partial_kernel<T, 3>), dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm, rs,
-                           d, ids, chain, k, N, partials, ctl, gd, vzero, nbr);
-    else
-        hipLaunchKernelGGL((p2plane_partial_kernel<T, 2>), dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm, rs,
-                           d, ids, chain, k, N, partials, ctl, gd, vzero, nbr);
+    auto* const kern = dim == 3 ? (sn ? p2plane_partial_kernel<T, 3, true> : p2plane_partial_kernel<T, 3, false>)
+                                : (sn ? p2plane_partial_kernel<T, 2, true> : p2plane_partial_kernel<T, 2, false>);
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, ctl,
+                       gd, vzero, nbr);
 }
 
 // Sum the per-block partials: one block per accumulator, each thread adds a
@@ -208,7 +219,7 @@ void launch_finalize(const double* partials, int nblocks, int nv, double* out, c
 // ------------------------------------------------------------ point-to-point --
 // pass 1: sum w, sum p*w, sum q*w (PointToPoint.cpp:67-72) + ErrorElements counts
 // layout: [0] sw, [1..3] sp, [4..6] sq, [7] kept, [8] nz, [9] rejM, [10] rejP
-template <typename T>
+template <typename T, bool SN>
 __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                             const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                             const int32_t* __restrict__ ids, WChain<T> chain, int k,
@@ -221,6 +232,8 @@ __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restr
         ctl_transform(ctl, Tm);
         ref = gd[ctl->level].gpts;
     }
+    SNPred<T> sn = chain.sn;  // (a copy: writing the kernel argument would move the chain to scratch)
+    if (SN) sn_bind(sn, ctl, gd);
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -235,7 +248,7 @@ __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restr
             const int64_t e = i * k + s;
             const T dv = d[e];
             // 0/1 weights, or a robust chain's real weight (point2point distance)
-            const T w = chain.robust ? robust_chain_weight(chain, wr, dv, e) : (chain_keep(wr, dv) ? (T)1 : (T)0);
+            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
             if (w != (T)0) acc[8] += 1.0;
             if (dv == inf) continue;
             if (w == (T)0) {
@@ -263,8 +276,8 @@ template <typename T>
 void launch_p2point_pass1(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
                           const WChain<T>& chain, int k, int64_t N, double* partials, const LoopCtl* ctl,
                           const GridDesc<T>* gd, hipStream_t s) {
-    hipLaunchKernelGGL(p2point_pass1_kernel<T>, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N,
-                       partials, ctl, gd);
+    auto* const kern = chain.sn.rn ? p2point_pass1_kernel<T, true> : p2point_pass1_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N, partials, ctl, gd);
 }
 
 // means in T: w_sum_inv = 1 / w.sum(); mean = sum * w_sum_inv (PointToPoint.cpp:67-72)
@@ -286,7 +299,7 @@ void launch_p2point_means(const double* sums, T* means_dev, int dim, const LoopC
 
 // pass 2: m = sum (qc * w) pc^T  (PointToPoint.cpp:76-81), 3x3 (2-D uses the
 // top-left 2x2; z terms are exactly zero)
-template <typename T>
+template <typename T, bool SN>
 __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                             const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                             const int32_t* __restrict__ ids, WChain<T> chain, int k,
@@ -300,6 +313,8 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
         ctl_transform(ctl, Tm);
         ref = gd[ctl->level].gpts;
     }
+    SNPred<T> sn = chain.sn;  // (a copy: writing the kernel argument would move the chain to scratch)
+    if (SN) sn_bind(sn, ctl, gd);
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -314,7 +329,7 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
             const T dv = d[e];
-            const T w = chain.robust ? robust_chain_weight(chain, wr, dv, e) : (chain_keep(wr, dv) ? (T)1 : (T)0);
+            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
             if (dv == inf || w == (T)0) continue;
             const P4<T> q4 = gld(ref, ids[e]);
             const T q[3] = {q4.x, q4.y, q4.z};
@@ -338,8 +353,9 @@ template <typename T>
 void launch_p2point_pass2(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
                           const WChain<T>& chain, int k, int64_t N, const T* means_dev, double* partials,
                           const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s) {
-    hipLaunchKernelGGL(p2point_pass2_kernel<T>, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N,
-                       means_dev, partials, ctl, gd);
+    auto* const kern = chain.sn.rn ? p2point_pass2_kernel<T, true> : p2point_pass2_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N, means_dev, partials,
+                       ctl, gd);
 }
 
 // Point-to-point in one pass (device loop): the sums both of the reference's
@@ -351,7 +367,7 @@ void launch_p2point_pass2(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, 
 // identity; the two-pass kernels above are the per-module path's).
 // Layout: [0] sum w, [1, 4) sum w p, [4, 7) sum w q, [7, 11) kept, nonzero
 // weights, rejected matches, rejected points, [11, 20) sum (w q_r) p_c.
-template <typename T>
+template <typename T, bool SN>
 __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                               const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                               const int32_t* __restrict__ ids, WChain<T> chain, int k,
@@ -364,6 +380,8 @@ __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __res
         ctl_transform(ctl, Tm);
         ref = gd[ctl->level].gpts;
     }
+    SNPred<T> sn = chain.sn;  // (a copy: writing the kernel argument would move the chain to scratch)
+    if (SN) sn_bind(sn, ctl, gd);
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -377,7 +395,7 @@ __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __res
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
             const T dv = d[e];
-            const T w = chain.robust ? robust_chain_weight(chain, wr, dv, e) : (chain_keep(wr, dv) ? (T)1 : (T)0);
+            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
             if (w != (T)0) acc[8] += 1.0;
             if (dv == inf) continue;
             if (w == (T)0) {
@@ -409,8 +427,8 @@ template <typename T>
 void launch_p2point_moments(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
                             const WChain<T>& chain, int k, int64_t N, double* partials, const LoopCtl* ctl,
                             const GridDesc<T>* gd, hipStream_t s) {
-    hipLaunchKernelGGL(p2point_moments_kernel<T>, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k,
-                       N, partials, ctl, gd);
+    auto* const kern = chain.sn.rn ? p2point_moments_kernel<T, true> : p2point_moments_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N, partials, ctl, gd);
 }
 
 // materialise the chain's weights (host mirror only); point-to-plane robust
