@@ -30,6 +30,11 @@
  *                         (ErrorMinimizer.cpp:58-193, PointToPlane.cpp:171-243)
  *   pmx_p2point_system  ErrorElements + PointToPoint weighted moments
  *                         (PointToPoint.cpp:61-81)
+ *   pmx_p2plane_covariance / pmx_loop_covariance
+ *                       the sums of PointToPlaneWithCovErrorMinimizer::
+ *                         estimateCovariance (ErrorMinimizers/
+ *                         PointToPlaneWithCov.cpp:72-162), read through
+ *                         ErrorMinimizer::getCovariance (PointMatcher.h:553)
  *   pmx_get_matches /   lazy host mirrors of Matches / OutlierWeights for
  *   pmx_get_weights       CPU modules and inspectors (PointMatcher.h:371-391)
  *
@@ -252,6 +257,24 @@ int pmx_p2plane_system(pmx_ctx* ctx, double* A, double* b, pmx_stats* st);
 /* Point-to-point: mean_p, mean_q (D each, T values), m = sum (qc w) pc^T
  * (D x D row-major, double sums of T products). */
 int pmx_p2point_system(pmx_ctx* ctx, double* mean_p, double* mean_q, double* m, pmx_stats* st);
+/* PointToPlaneWithCovErrorMinimizer::estimateCovariance
+ * (ErrorMinimizers/PointToPlaneWithCov.cpp:72-162) for the last pmx_match, its
+ * recorded filter chain and its T_iter; callable after pmx_p2plane_system.
+ * T_step (rows x rows row-major T) is the increment the caller solved from
+ * that system; alpha, beta, gamma, t_x, t_y, t_z are derived from it in T as
+ * :94-99.  Over the ErrorElements columns (dist != inf && w != 0; a robust
+ * weight's value is not used, :106-150) it returns
+ *   H = sum a a^T                (J_hessian, :136-138)
+ *   Q = sum (u u^T + v v^T)      (d2J_dZdX d2J_dZdX^T, :140-158)
+ * as 6 x 6 row-major full symmetric matrices, fp64 sums of T-precision
+ * products, and the number of columns in *pairs (may be NULL); global over
+ * all ranks (one all-reduce).  The covariance is sensorStdDev^2 H^-1 Q H^-1
+ * (:156-161), left to the caller.  The point ranges in a, u, v are norms in
+ * the centred reference frame, as the reference computes them (:116-119), not
+ * sensor ranges; a zero range gives NaN.  Synchronises the stream.
+ * PMX_E_BAD_PARAM for a 2-D context or a reference without normals (the
+ * reference returns max * I there, :91-92); PMX_E_STATE without a match. */
+int pmx_p2plane_covariance(pmx_ctx* ctx, const void* T_step, double* H, double* Q, int64_t* pairs);
 
 /* ---------------------------------------------------------- host mirrors --- */
 /* dists: k x N T (point-major), ids: k x N int32 (this rank's shard) */
@@ -289,8 +312,8 @@ int pmx_sync(pmx_ctx* ctx);
  * among default / Null / MaxDist / MinDist / MedianDist / TrimmedDist /
  * VarTrimmedDist / Robust (at most one; with PointToPoint only its
  * point2point distance) / SurfaceNormal (at most one; filter_p[i][0] = eps
- * = cos(maxAngle) in T), PointToPlane (no force2D / force4DOF) or
- * PointToPoint, checkers among Counter / Differential (smoothLength < 64) /
+ * = cos(maxAngle) in T), PointToPlane (no force2D / force4DOF), with or
+ * without the covariance, or PointToPoint, checkers among Counter / Differential (smoothLength < 64) /
  * Bound.  Otherwise pmx_loop_begin returns PMX_E_BAD_PARAM and the caller
  * keeps the per-module calls. */
 enum { PMX_CHECK_COUNTER = 0, PMX_CHECK_DIFFERENTIAL = 1, PMX_CHECK_BOUND = 2 };
@@ -305,7 +328,8 @@ typedef struct pmx_loop_cfg {
     int n_filters;              /* 0: the empty chain's default (dist != inf) */
     int filter_kind[8];         /* PMX_FILTER_* */
     double filter_p[8][3];      /* maxDist / minDist / factor / ratio / (minRatio, maxRatio, lambda) / eps */
-    int minimizer;              /* 0 PointToPlane, 1 PointToPoint */
+    int minimizer;              /* 0 PointToPlane, 1 PointToPoint, 2 PointToPlane with covariance
+                                   (PointToPlane's iterations; pmx_loop_covariance afterwards) */
     int n_checkers;
     int checker_kind[8];        /* PMX_CHECK_* */
     double checker_p[8][3];     /* Counter: max; Differential: rot, trans, smoothLength; Bound: rot, trans */
@@ -343,6 +367,15 @@ int pmx_loop_begin(pmx_ctx* ctx, const pmx_loop_cfg* cfg, const void* T_iter0);
  * the error the ICP raised (st->error, message in pmx_last_error), or a
  * HIP / RCCL / state error. */
 int pmx_loop_run(pmx_ctx* ctx, int n, pmx_loop_status* st);
+/* pmx_p2plane_covariance for a finished loop begun with minimizer 2
+ * (PointToPlaneWithCovErrorMinimizer::compute keeps the estimate of every
+ * iteration and getCovariance returns the last, PointToPlaneWithCov.cpp:61-69,
+ * 165-169: only that one is computed): H, Q and *pairs of the last iteration
+ * that reached the minimiser, at the transform its match ran at and the
+ * increment its step solved, both still on the device.  PMX_E_STATE while the
+ * loop is not done, after a loop that stopped on an error, or one begun with
+ * another minimizer; PMX_E_BAD_PARAM for a 2-D context. */
+int pmx_loop_covariance(pmx_ctx* ctx, double* H, double* Q, int64_t* pairs);
 /* T_iter after each completed iteration (keep_trace): count x rows x rows T */
 int pmx_loop_trace(pmx_ctx* ctx, int first, int count, void* out);
 /* Quantile window statistics of the device loop (no reference counterpart;

@@ -99,6 +99,13 @@ int pmx_icp_iterate(pmx_icp* icp, int n, int* done);
 int pmx_icp_finish(pmx_icp* icp, void* T_out);
 
 int pmx_icp_stats_get(const pmx_icp* icp, pmx_icp_stats* out);
+/* errorMinimizer->getCovariance() (PointMatcher.h:553, ErrorMinimizer.cpp:
+ * 266-270) after a compute: 6 x 6 row-major T into cov36.  With
+ * PointToPlaneWithCovErrorMinimizer the estimate of the last iteration,
+ * sensorStdDev^2 H^-1 Q H^-1 (PointToPlaneWithCov.cpp:72-162; max * I for a
+ * 2-D ICP, :91-92), computed once when the loop stops; zeros for every other
+ * minimiser. */
+int pmx_icp_covariance(pmx_icp* icp, void* cov36);
 /* T_iter after each iteration (rows x rows each), returns count written */
 int pmx_icp_trace_get(const pmx_icp* icp, void* out, int max_iters);
 /* HIP-event device time of the match kernel over the last iterations */

@@ -154,7 +154,7 @@ EXPORTS = [
     "pmx_outlier_default", "pmx_outlier_null", "pmx_outlier_maxdist", "pmx_outlier_mindist",
     "pmx_outlier_mediandist", "pmx_outlier_trimmed", "pmx_outlier_vartrimmed", "pmx_outlier_robust",
     "pmx_robust_scale", "pmx_set_reading_radii", "pmx_set_reading_normals", "pmx_outlier_surface_normal",
-    "pmx_p2plane_system", "pmx_p2point_system", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
+    "pmx_p2plane_system", "pmx_p2point_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid",
@@ -201,6 +201,8 @@ def lib():
         l.pmx_p2plane_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         l.pmx_p2point_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(Stats)]
+        l.pmx_p2plane_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        l.pmx_loop_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         l.pmx_get_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         l.pmx_get_weights.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_vartrim_partial_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
@@ -526,6 +528,24 @@ class Context:
         self._chk(self._l.pmx_p2point_system(self.h, _ptr(mp), _ptr(mq), _ptr(m), C.byref(st)))
         return mp, mq, m.reshape(D, D), st
 
+    def p2plane_covariance(self, T_step):
+        """The sums of PointToPlaneWithCovErrorMinimizer's estimate for the last
+        match and the solved increment T_step (pmx_p2plane_covariance):
+        (H, Q, pairs), 6 x 6 float64 each; cov = sigma^2 H^-1 Q H^-1."""
+        T_step = self._arr(T_step)
+        H, Q = np.zeros((6, 6)), np.zeros((6, 6))
+        n = C.c_int64(0)
+        self._chk(self._l.pmx_p2plane_covariance(self.h, _ptr(T_step), _ptr(H), _ptr(Q), C.byref(n)))
+        return H, Q, n.value
+
+    def loop_covariance(self):
+        """The same for the last iteration of a finished device loop begun with
+        PointToPlaneWithCovErrorMinimizer (pmx_loop_covariance)."""
+        H, Q = np.zeros((6, 6)), np.zeros((6, 6))
+        n = C.c_int64(0)
+        self._chk(self._l.pmx_loop_covariance(self.h, _ptr(H), _ptr(Q), C.byref(n)))
+        return H, Q, n.value
+
     def get_matches(self):
         d = np.empty((self.N, self.knn), self.dtype)
         i = np.empty((self.N, self.knn), np.int32)
@@ -572,7 +592,8 @@ class Context:
             cfg.filter_kind[i] = FILTER_KIND[name]
             for j, v in enumerate(p):
                 cfg.filter_p[i][j] = float(v)
-        cfg.minimizer = 0 if minimizer.startswith("PointToPlane") else 1
+        cfg.minimizer = (2 if minimizer.startswith("PointToPlaneWithCov")
+                         else 0 if minimizer.startswith("PointToPlane") else 1)
         cfg.n_checkers = len(checkers)
         for i, (name, *p) in enumerate(checkers):
             cfg.checker_kind[i] = CHECK_KIND[name]

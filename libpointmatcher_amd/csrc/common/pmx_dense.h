@@ -621,4 +621,62 @@ PMX_HD void p2point_transform(int rows, const T* m, const T* mp, const T* mq, T*
     out[D * rows + D] = 1;
 }
 
+// PointToPlaneWithCov: Matrix::inverse() of the 6 x 6 Hessian
+// (PointToPlaneWithCov.cpp:156; Eigen inverts a dynamic matrix by
+// PartialPivLU): LU with row pivoting, then the identity's columns solved.  A
+// zero pivot is divided by like any other: a singular matrix gives inf / NaN
+// entries and raises nothing, as the reference.  Host only (once per ICP).
+template <typename T>
+inline void lu_inverse(const T* A, int n, T* inv) {  // n <= 6
+    T lu[36];
+    int perm[6];
+    for (int i = 0; i < n * n; ++i) lu[i] = A[i];
+    for (int i = 0; i < n; ++i) perm[i] = i;
+    for (int k = 0; k < n; ++k) {
+        int p = k;
+        T best = fabs(lu[k * n + k]);
+        for (int r = k + 1; r < n; ++r)
+            if (fabs(lu[r * n + k]) > best) {
+                best = fabs(lu[r * n + k]);
+                p = r;
+            }
+        if (p != k) {
+            for (int c = 0; c < n; ++c) vswap(lu[k * n + c], lu[p * n + c]);
+            const int t = perm[k];
+            perm[k] = perm[p];
+            perm[p] = t;
+        }
+        for (int r = k + 1; r < n; ++r) {
+            const T f = lu[r * n + k] / lu[k * n + k];
+            lu[r * n + k] = f;
+            for (int c = k + 1; c < n; ++c) lu[r * n + c] = lu[r * n + c] - f * lu[k * n + c];
+        }
+    }
+    for (int j = 0; j < n; ++j) {  // column j of the inverse: L U x = P e_j
+        T y[6];
+        for (int r = 0; r < n; ++r) {
+            T s = perm[r] == j ? (T)1 : (T)0;
+            for (int c = 0; c < r; ++c) s = s - lu[r * n + c] * y[c];
+            y[r] = s;
+        }
+        for (int r = n - 1; r >= 0; --r) {
+            T s = y[r];
+            for (int c = r + 1; c < n; ++c) s = s - lu[r * n + c] * inv[c * n + j];
+            inv[r * n + j] = s / lu[r * n + r];
+        }
+    }
+}
+
+// C = A * B for n <= 6 (matmul above holds 4 x 4), sequential inner sums; C
+// may not alias A or B
+template <typename T>
+inline void matmul6(const T* A, const T* B, int n, T* C) {
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) {
+            T s = A[r * n] * B[c];
+            for (int k = 1; k < n; ++k) s = s + A[r * n + k] * B[k * n + c];
+            C[r * n + c] = s;
+        }
+}
+
 }  // namespace pmx_dense

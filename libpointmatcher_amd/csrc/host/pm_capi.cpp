@@ -157,6 +157,14 @@ void finish_impl(pmx_icp* icp, void* T_out) {
 }
 
 template <typename T>
+void covariance_impl(pmx_icp* icp, void* cov36) {
+    auto& I = get<T>(icp);
+    if (!I.errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
+    const std::vector<T> c = I.errorMinimizer->getCovariance();
+    std::memcpy(cov36, c.data(), sizeof(T) * 36);
+}
+
+template <typename T>
 void stats_impl(const pmx_icp* icp, pmx_icp_stats* s) {
     auto& I = get<T>(const_cast<pmx_icp*>(icp));
     std::memset(s, 0, sizeof(*s));
@@ -359,6 +367,11 @@ int pmx_icp_stats_get(const pmx_icp* icp, pmx_icp_stats* out) {
     else
         stats_impl<float>(icp, out);
     return PMX_ICP_OK;
+}
+
+int pmx_icp_covariance(pmx_icp* icp, void* cov36) {
+    if (!icp || !cov36) return PMX_ICP_INVALID_PARAMETER;
+    return guarded(icp, [&] { BOTH(icp, covariance_impl<float>(icp, cov36), covariance_impl<double>(icp, cov36)); });
 }
 
 int pmx_icp_trace_get(const pmx_icp* icp, void* out, int max_iters) {

@@ -5,8 +5,9 @@
 //   KDTreeMatcher, KDTreeVarDistMatcher  MatchersImpl.h:74-134
 //   Null/MaxDist/MinDist/MedianDist/TrimmedDist/VarTrimmedDist/Robust OutlierFilter
 //                                 OutlierFiltersImpl.h:51-260
-//   PointToPlane / PointToPoint ErrorMinimizer
-//                                 ErrorMinimizers/PointToPlane.h:61-90, PointToPoint.h
+//   PointToPlane / PointToPlaneWithCov / PointToPoint ErrorMinimizer
+//                                 ErrorMinimizers/PointToPlane.h:61-90, PointToPlaneWithCov.h:60-86,
+//                                 PointToPoint.h
 //   Counter / Differential / Bound TransformationChecker
 //                                 TransformationCheckersImpl.h:60-130
 //   Identity / SurfaceNormal / MaxDist / MinDist / RandomSampling / FixStepSampling /
@@ -467,7 +468,10 @@ struct PointToPlaneEM : PM<T>::ErrorMinimizer {
                      "0", "0", "1", &Parametrizable::Comp<bool>)};
     }
     explicit PointToPlaneEM(const Parametrizable::Parameters& p)
-        : PM<T>::ErrorMinimizer("PointToPlaneErrorMinimizer", doc(), p),
+        : PointToPlaneEM("PointToPlaneErrorMinimizer", doc(), p) {}
+    // (a derived minimiser's name and parameters, PointToPlane.cpp:66-76)
+    PointToPlaneEM(const std::string& name, const Parametrizable::ParametersDoc& d, const Parametrizable::Parameters& p)
+        : PM<T>::ErrorMinimizer(name, d, p),
           force2D(this->template get<T>("force2D") != (T)0),
           force4DOF(this->template get<T>("force4DOF") != (T)0) {
         if (force2D && force4DOF)
@@ -492,6 +496,53 @@ struct PointToPlaneEM : PM<T>::ErrorMinimizer {
     bool loopConfig(pmx_loop_cfg& cfg) const override {
         cfg.minimizer = 0;
         return !force2D && !force4DOF;
+    }
+};
+
+// PointToPlaneWithCovErrorMinimizer (ErrorMinimizers/PointToPlaneWithCov.cpp):
+// PointToPlane's transforms, and the covariance of the last iteration's
+// estimate (Censi's closed form, :72-162).  The reference estimates it in
+// every compute and getCovariance returns the last (:61-69, 165-169); here it
+// is estimated once, when the loop has stopped.  The two 6 x 6 sums over the
+// kept pairs come from the device (pmx_p2plane_covariance /
+// pmx_loop_covariance); the inverse and the products are the reference's, in T.
+template <typename T>
+struct PointToPlaneWithCovEM : PointToPlaneEM<T> {
+    const T sensorStdDev;
+    std::vector<T> covMatrix;
+    static Parametrizable::ParametersDoc doc() {
+        Parametrizable::ParametersDoc d = PointToPlaneEM<T>::doc();
+        d.push_back(PDoc("sensorStdDev", "sensor standard deviation", "0.01", "0.", "inf", &Parametrizable::Comp<T>));
+        return d;
+    }
+    explicit PointToPlaneWithCovEM(const Parametrizable::Parameters& p)
+        : PointToPlaneEM<T>("PointToPlaneWithCovErrorMinimizer", doc(), p),
+          sensorStdDev(this->template get<T>("sensorStdDev")),
+          covMatrix(36, (T)0) {}
+    bool loopConfig(pmx_loop_cfg& cfg) const override {
+        cfg.minimizer = 2;  // (PointToPlane's iterations; the step keeps the increments)
+        return !this->force2D && !this->force4DOF;
+    }
+    std::vector<T> getCovariance() const override { return covMatrix; }
+    void loopStopped(Device& d, int rows, const T* dT) override {
+        covMatrix.assign(36, (T)0);
+        if (rows != 4) {  // normals.rows() < 3 (PointToPlaneWithCov.cpp:91-92)
+            for (int i = 0; i < 6; ++i) covMatrix[(size_t)i * 7] = std::numeric_limits<T>::max();
+            return;
+        }
+        double H[36], Q[36];
+        int64_t pairs = 0;
+        d.check(dT ? pmx_p2plane_covariance(d.ctx, dT, H, Q, &pairs) : pmx_loop_covariance(d.ctx, H, Q, &pairs));
+        T Ht[36], Qt[36], Hi[36], HiQ[36], cov[36];
+        for (int i = 0; i < 36; ++i) {
+            Ht[i] = (T)H[i];
+            Qt[i] = (T)Q[i];
+        }
+        dense::lu_inverse(Ht, 6, Hi);      // J_hessian.inverse(), :156
+        dense::matmul6(Hi, Qt, 6, HiQ);    // inv_J_hessian * covariance * inv_J_hessian, :159
+        dense::matmul6(HiQ, Hi, 6, cov);
+        const T s2 = sensorStdDev * sensorStdDev;  // :161
+        for (int i = 0; i < 36; ++i) covMatrix[(size_t)i] = s2 * cov[i];
     }
 };
 
@@ -1189,6 +1240,8 @@ PointMatcher<T>::PointMatcher() {
                                [](const Ps& p) { return std::make_shared<SurfaceNormalOF<T>>(p); }, true);
     ErrorMinimizerRegistrar.reg("PointToPlaneErrorMinimizer",
                                 [](const Ps& p) { return std::make_shared<PointToPlaneEM<T>>(p); }, true);
+    ErrorMinimizerRegistrar.reg("PointToPlaneWithCovErrorMinimizer",
+                                [](const Ps& p) { return std::make_shared<PointToPlaneWithCovEM<T>>(p); }, true);
     ErrorMinimizerRegistrar.reg("PointToPointErrorMinimizer",
                                 [](const Ps& p) { return std::make_shared<PointToPointEM<T>>(p); }, false);
     TransformationCheckerRegistrar.reg("CounterTransformationChecker",
@@ -1697,6 +1750,9 @@ bool PointMatcher<T>::ICP::iterate(int n) {
     if (st.reason == 1) maxNumIterationsReached = true;
     if (st.done) iterate_ = false;
     if (rc != PMX_OK) dev.check(rc);  // the exception the loop raised
+    // (stopped by a checker: the last iteration's match is still resident,
+    // nothing has replaced it yet)
+    if (st.done && fresh > 0) errorMinimizer->loopStopped(dev, dim, nullptr);
     return iterate_;
 }
 
@@ -1729,6 +1785,8 @@ bool PointMatcher<T>::ICP::stepModules() {
     }
     ++iterationCount;
     if (keepTrace) trace.push_back(T_iter_);
+    // (the loop has stopped: this iteration's match is still resident)
+    if (!iterate_) errorMinimizer->loopStopped(dev, dim, dT.data());
     return iterate_;
 }
 

@@ -120,6 +120,15 @@ struct PointMatcher {
         virtual ~ErrorMinimizer() {}
         virtual TransformationParameters compute(Device& dev, int rows) = 0;
         virtual bool loopConfig(pmx_loop_cfg&) const { return false; }
+        // ErrorMinimizer::getCovariance (ErrorMinimizer.cpp:266-270): 6 x 6
+        // row-major, zeros unless the minimiser estimates one
+        virtual std::vector<T> getCovariance() const { return std::vector<T>(36, (T)0); }
+        // Once per ICP, when a checker has stopped the loop and its last match
+        // is still resident on the device (the reference's minimisers that
+        // keep per-iteration results expose only the last one).  dT: the last
+        // iteration's increment (rows x rows) after the module calls, null
+        // after the device loop, which holds it itself.
+        virtual void loopStopped(Device&, int /*rows*/, const T* /*dT*/) {}
         T getPointUsedRatio() const { return pointUsedRatio; }
         T getWeightedPointUsedRatio() const { return weightedPointUsedRatio; }
         virtual T getOverlap() const { return weightedPointUsedRatio; }

@@ -1590,6 +1590,50 @@ int p2point_impl(pmx_ctx* c, double* mean_p, double* mean_q, double* m, pmx_stat
     return PMX_OK;
 }
 
+// PointToPlaneWithCovErrorMinimizer::estimateCovariance's sums
+// (PointToPlaneWithCov.cpp:72-162) for the resident match, its chain record
+// and step transform; Tinc (rows x rows row-major T) the solved increment
+template <typename T>
+int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* pairs) {
+    if (c->d_ref && (c->dim != 3 || !c->has_normals))  // (normals.rows() < 3, PointToPlaneWithCov.cpp:91)
+        return fail(c, PMX_E_BAD_PARAM, "PointToPlaneWithCovErrorMinimizer: the covariance needs a 3-D reference with \"normals\"");
+    int rc = check_match(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // alpha, beta, gamma, t_x, t_y, t_z in T (PointToPlaneWithCov.cpp:94-99)
+    const int R = c->rows;
+    CovParams<T> cp;
+    cp.beta = -std::asin(Tinc[2 * R + 0]);
+    cp.alpha = std::atan2(Tinc[2 * R + 1], Tinc[2 * R + 2]);
+    cp.gamma = std::atan2(Tinc[1 * R + 0] / std::cos(cp.beta), Tinc[0 * R + 0] / std::cos(cp.beta));
+    cp.tx = Tinc[0 * R + 3];
+    cp.ty = Tinc[1 * R + 3];
+    cp.tz = Tinc[2 * R + 3];
+    const WChain<T> chain = chain_of<T>(c);
+    const bool nbr = nbr_with_normals(c) && !chain.robust;  // (the records p2plane_enqueue reads)
+    // the second half of the iteration block's result area: the step's
+    // system and the statistics in the first half stay as the minimiser left them
+    double* out = c->d_result + 64;
+    static_assert(64 + kCovNV <= 128 && kCovNV <= kNVMax, "iteration block layout");
+    launch_p2plane_cov<T>((const P4<T>*)c->d_rd, step_mat<T>(c), (const P4<T>*)match_pn(c),
+                          (const P4<T>*)match_nrm(c), match_rs(c), (const T*)c->d_dists, c->d_ids, chain, c->knn, c->N,
+                          cp, c->d_partials, c->stream, nbr ? (const P4<T>*)c->d_nbr : nullptr);
+    launch_finalize(c->d_partials, kRedBlocks, kCovNV, out, nullptr, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = allreduce_f64(c, out, kCovNV))) return rc;  // (several ranks: the one extra collective per ICP)
+    double r[kCovNV];
+    HIPCHK(c, hipMemcpyAsync(r, out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int a = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j, ++a) {
+            H[i * 6 + j] = H[j * 6 + i] = r[a];
+            Q[i * 6 + j] = Q[j * 6 + i] = r[kCovQ + a];
+        }
+    if (pairs) *pairs = (int64_t)r[kCovCount];
+    return PMX_OK;
+}
+
 template <typename T>
 int get_matches_impl(pmx_ctx* c, void* dists, int32_t* ids) {
     int rc = check_match(c);
@@ -1645,6 +1689,7 @@ int get_weights_impl(pmx_ctx* c, void* w) {
     template int outlier_robust_impl<T>(pmx_ctx*, int, int, double, double, int, double, int); \
     template int p2plane_enqueue<T>(pmx_ctx*);                                              \
     template int p2point_enqueue<T>(pmx_ctx*);                                              \
+    template int p2plane_cov_impl<T>(pmx_ctx*, const T*, double*, double*, int64_t*);       \
     template int get_matches_impl<T>(pmx_ctx*, void*, int32_t*);                            \
     template int unpermute<T>(pmx_ctx*, const std::vector<T>&, T*, int);
 PMX_INST(float)
@@ -1731,6 +1776,12 @@ int pmx_outlier_surface_normal(pmx_ctx* c, int pos, double eps) { return OUTLIER
 int pmx_p2plane_system(pmx_ctx* c, double* A, double* b, pmx_stats* st) {
     if (!c || !A || !b) return fail(c, PMX_E_BAD_PARAM, "null argument");
     return DISPATCH(c, p2plane_impl<float>(c, A, b, st), p2plane_impl<double>(c, A, b, st));
+}
+
+int pmx_p2plane_covariance(pmx_ctx* c, const void* T_step, double* H, double* Q, int64_t* pairs) {
+    if (!c || !T_step || !H || !Q) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    return DISPATCH(c, p2plane_cov_impl<float>(c, (const float*)T_step, H, Q, pairs),
+                    p2plane_cov_impl<double>(c, (const double*)T_step, H, Q, pairs));
 }
 
 int pmx_p2point_system(pmx_ctx* c, double* mp, double* mq, double* m, pmx_stats* st) {

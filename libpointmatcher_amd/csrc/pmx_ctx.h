@@ -12,6 +12,7 @@
 
 #include "pmx_internal.h"
 #include "pmx_p2plane.h"
+#include "pmx_cov.h"
 #include "pmx_spec.h"
 
 #include <rccl/rccl.h>
@@ -326,6 +327,8 @@ struct pmx_ctx {
     int64_t loop_issued = 0;      // iterations enqueued since pmx_loop_begin
     int loop_iters = 0;           // iterations completed (last status)
     bool loop_done = false;       // the loop has stopped (last status)
+    int loop_err = 0;             // its device error word (last status)
+    bool loop_cov = false;        // pmx_loop_cfg.minimizer 2: the step keeps the increments (pmx_loop_covariance)
 
     // timing of the match kernel
     bool timing = false;
@@ -417,6 +420,8 @@ template <typename T>
 int p2plane_enqueue(pmx_ctx* c);
 template <typename T>
 int p2point_enqueue(pmx_ctx* c);
+template <typename T>
+int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* pairs);
 template <typename T>
 int get_matches_impl(pmx_ctx* c, void* dists, int32_t* ids);
 template <typename V>

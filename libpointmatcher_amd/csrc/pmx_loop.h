@@ -52,6 +52,7 @@ struct LoopCfg {
     int knn;
     int tile_dispatch;  // both match forms enqueued; the step picks the next (pmx_step.h)
     int p2p_onepass;    // point-to-point: one moments pass (launch_p2point_moments layout), the step centres
+    int keep_increment;  // the step keeps each solved increment in LoopState.dT (pmx_loop_covariance reads the last)
 };
 
 template <typename T>
@@ -75,6 +76,7 @@ struct LoopState {
     double level_cells[kMaxLevels];
     long long level_seen[kMaxLevels];
     T xsolve[6];  // the rank-deficient solve's result (loop_solve_rank_deficient)
+    T dT[16];     // the last minimised iteration's increment, rows x rows (LoopCfg.keep_increment)
 };
 
 template <typename T>

@@ -28,7 +28,13 @@ constexpr size_t kLoopStage = 256 + ((sizeof(SpecSel) + 255) & ~(size_t)255);
 
 
 template <typename T>
-int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg, const T* T0) {
+int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
+    // minimizer 2 (PointToPlaneWithCovErrorMinimizer) runs PointToPlane's
+    // iterations; the step only keeps each increment for pmx_loop_covariance
+    pmx_loop_cfg cfg_pl = *cfg_in;
+    const bool with_cov = cfg_in->minimizer == 2;
+    if (with_cov) cfg_pl.minimizer = 0;
+    const pmx_loop_cfg* cfg = &cfg_pl;
     if (!c->d_ref) return fail(c, PMX_E_STATE, "no reference (Matcher::init not called)");
     if (!c->d_rd && c->N > 0) return fail(c, PMX_E_STATE, "no reading");
     if (c->search_type == 0 || !c->grid_ready || c->grid_mode == 0)
@@ -105,6 +111,7 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg, const T* T0) {
     // (double only: in float the reference centres in T before its products,
     // and the one-pass form drifted 1.05e-5 from the per-module path over 25
     // iterations, past the 1e-5 bar; in double both are far inside 1e-12)
+    d.keep_increment = with_cov ? 1 : 0;
     d.p2p_onepass = cfg->minimizer == 1 && c->p2p_onepass && c->dtype == PMX_F64 ? 1 : 0;
     int rc;
     size_t cap = 0;
@@ -167,6 +174,8 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg, const T* T0) {
     c->loop_issued = 0;
     c->loop_iters = 0;
     c->loop_done = false;
+    c->loop_cov = with_cov;
+    c->loop_err = 0;
     c->shard_done_seen = false;
     c->shard_hit_streak = 0;
     c->shard_replay = false;
@@ -401,6 +410,7 @@ int loop_run_impl(pmx_ctx* c, int n, pmx_loop_status* st) {
     const LoopState<T>& S = *(const LoopState<T>*)(fin + kStatLoop);
     c->loop_iters = S.iter;
     c->loop_done = S.done != 0;
+    c->loop_err = S.err;
     c->level = ctl.level;
     c->ids_level = S.last_level;
     if (S.iter > 0 || S.err)  // the last executed match's step transform (LoopCtl.T moved on)
@@ -466,6 +476,25 @@ int loop_run_impl(pmx_ctx* c, int n, pmx_loop_status* st) {
     return err;
 }
 
+// pmx_loop_covariance: the finished loop left its last minimised iteration's
+// match, limits and step transform resident (every kernel enqueued after the
+// stop returned at once; loop_run_impl copied LoopCtl.Tprev into Tstep), so
+// the module path's reduction runs on them with the increment the step kept
+template <typename T>
+int loop_cov_impl(pmx_ctx* c, double* H, double* Q, int64_t* pairs) {
+    if (!c->loop_begun || !c->loop_done || c->loop_err)
+        return fail(c, PMX_E_STATE, "pmx_loop_covariance: the device loop has not finished, or stopped on an error");
+    if (!c->loop_cov)
+        return fail(c, PMX_E_STATE, "pmx_loop_covariance: the loop was not configured with minimizer 2");
+    if (c->dim != 3 || !c->has_normals)
+        return fail(c, PMX_E_BAD_PARAM, "PointToPlaneWithCovErrorMinimizer: the covariance needs a 3-D reference with \"normals\"");
+    T dT[16];
+    const LoopState<T>* S = (const LoopState<T>*)c->d_loop;
+    HIPCHK(c, hipMemcpyAsync(dT, S->dT, sizeof(dT), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return p2plane_cov_impl<T>(c, dT, H, Q, pairs);
+}
+
 template <typename T>
 int loop_trace_impl(pmx_ctx* c, int first, int count, void* out) {
     if (!c->loop_begun || !c->loop_cfg.keep_trace) return fail(c, PMX_E_STATE, "no loop trace (keep_trace = 0)");
@@ -494,6 +523,12 @@ int pmx_loop_run(pmx_ctx* c, int n, pmx_loop_status* st) {
     if (!c) return PMX_E_BAD_PARAM;
     (void)hipSetDevice(c->device);
     return DISPATCH(c, loop_run_impl<float>(c, n, st), loop_run_impl<double>(c, n, st));
+}
+
+int pmx_loop_covariance(pmx_ctx* c, double* H, double* Q, int64_t* pairs) {
+    if (!c || !H || !Q) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c, loop_cov_impl<float>(c, H, Q, pairs), loop_cov_impl<double>(c, H, Q, pairs));
 }
 
 int pmx_loop_trace(pmx_ctx* c, int first, int count, void* out) {

@@ -14,6 +14,18 @@ __device__ __forceinline__ void xform3(const Mat4<T>& M, const P4<T>& p, T& x, T
     z = ((M.m[8] * p.x + M.m[9] * p.y) + M.m[10] * p.z) + M.m[11] * p.w;
 }
 
+// the squared point-to-plane distance of a RobustOutlierFilter with
+// distanceType point2plane (computePointToPlaneDistance,
+// OutlierFiltersImpl.cpp:460-489), with the normalised reference normal
+template <typename T>
+__device__ __forceinline__ T p2pl_distance(T px, T py, T pz, const P4<T>& q, const P4<T>& n) {
+    // Eigen normalized(): v / sqrt(squaredNorm), v itself when the norm is 0
+    const T sq = (n.x * n.x + n.y * n.y) + n.z * n.z;
+    const T nn = sq > (T)0 ? sqrt(sq) : (T)1;
+    const T dot = ((n.x / nn) * (px - q.x) + (n.y / nn) * (py - q.y)) + (n.z / nn) * (pz - q.z);
+    return dot * dot;  // (pow(dot, 2) rounds to the same T)
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

@@ -38,14 +38,6 @@ __device__ __forceinline__ T robust_chain_weight(const WChain<T>& c, const WRang
     const T e2 = dist / (s * s);
     return pred * robust_weight<T>(c.rb_fct, c.rb_k, c.rb_sqa, e2);
 }
-template <typename T>
-__device__ __forceinline__ T p2pl_distance(T px, T py, T pz, const P4<T>& q, const P4<T>& n) {
-    // Eigen normalized(): v / sqrt(squaredNorm), v itself when the norm is 0
-    const T sq = (n.x * n.x + n.y * n.y) + n.z * n.z;
-    const T nn = sq > (T)0 ? sqrt(sq) : (T)1;
-    const T dot = ((n.x / nn) * (px - q.x) + (n.y / nn) * (py - q.y)) + (n.z / nn) * (pz - q.z);
-    return dot * dot;  // (pow(dot, 2) rounds to the same T)
-}
 
 // The chain's weight of entry e (slot i) in the point-to-point reductions.
 // SN (the chain holds the SurfaceNormalOutlierFilter): times the filter's 0/1,

@@ -242,6 +242,10 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
         }
         p2point_transform(rows, m, mp, mq, dT);
     }
+    if (cfg.keep_increment) {  // (PointToPlaneWithCovErrorMinimizer: the covariance is estimated at it)
+#pragma unroll
+        for (int i = 0; i < ROWS * ROWS; ++i) S->dT[i] = dT[i];
+    }
     matmul(dT, Tit, rows, Tit);
 #pragma unroll
     for (int i = 0; i < ROWS * ROWS; ++i) S->Titer[i] = Tit[i];

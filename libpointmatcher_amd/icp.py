@@ -85,6 +85,7 @@ def lib():
         l.pmx_icp_finish.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_icp_stats_get.argtypes = [C.c_void_p, C.POINTER(IcpStats)]
         l.pmx_icp_trace_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        l.pmx_icp_covariance.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_icp_timing.argtypes = [C.c_void_p, C.c_int]
         l.pmx_icp_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         l.pmx_icp_select_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -260,6 +261,14 @@ class ICP:
         out = np.zeros((max(it, 1), self.rows, self.rows), self.dtype)
         n = self._l.pmx_icp_trace_get(self.h, _p(out), min(it, max_iters))
         return out[:n]
+
+    def covariance(self):
+        """errorMinimizer->getCovariance() of the last compute (pmx_icp_covariance):
+        6 x 6, the estimate of PointToPlaneWithCovErrorMinimizer (translation
+        first, then the rotation angles), zeros for every other minimiser."""
+        out = np.zeros((6, 6), self.dtype)
+        self._chk(self._l.pmx_icp_covariance(self.h, _p(out)))
+        return out
 
     def timing(self, on=True):
         self._chk(self._l.pmx_icp_timing(self.h, 1 if on else 0))
