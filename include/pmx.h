@@ -30,6 +30,10 @@
  *                         (ErrorMinimizer.cpp:58-193, PointToPlane.cpp:171-243)
  *   pmx_p2point_system  ErrorElements + PointToPoint weighted moments
  *                         (PointToPoint.cpp:61-81)
+ *   pmx_p2point_similarity_system
+ *                       the same, and sigma = sum ||pc||^2 w of
+ *                         PointToPointSimilarityErrorMinimizer::compute
+ *                         (ErrorMinimizers/PointToPointSimilarity.cpp:43-98)
  *   pmx_p2plane_covariance / pmx_loop_covariance
  *                       the sums of PointToPlaneWithCovErrorMinimizer::
  *                         estimateCovariance (ErrorMinimizers/
@@ -47,7 +51,9 @@
  *   PMX_E_NO_POINTS       -> ConvergenceError("ErrorMnimizer: no point to minimize")
  *   PMX_E_EMPTY_QUANTILE  -> ConvergenceError("no outlier to filter")
  *   PMX_E_BAD_PARAM       -> InvalidParameter
- *   PMX_E_TRANSFORMATION  -> TransformationError (device loop)
+ *   PMX_E_TRANSFORMATION  -> TransformationError (device loop; not with the
+ *                            similarity minimiser, whose transformation
+ *                            checks nothing, TransformationsImpl.cpp:197-203)
  *   PMX_E_CONVERGENCE     -> ConvergenceError (device loop checkers)
  *   PMX_E_HIP / PMX_E_RCCL / PMX_E_STATE -> std::runtime_error
  */
@@ -69,7 +75,9 @@ enum {
     PMX_E_NO_POINTS = -1,
     PMX_E_EMPTY_QUANTILE = -2,
     PMX_E_BAD_PARAM = -3,
-    PMX_E_TRANSFORMATION = -4, /* device loop: T_iter not rigid */
+    PMX_E_TRANSFORMATION = -4, /* device loop: T_iter not rigid (|1 - det R| > 1e-3).  It cannot occur in a
+                                  loop begun with minimizer 3 (PointToPointSimilarity): that chain holds a
+                                  SimilarityTransformation and the determinant is not checked */
     PMX_E_CONVERGENCE = -5,    /* device loop: a checker raised ConvergenceError */
     PMX_E_HIP = -10,
     PMX_E_RCCL = -11,
@@ -257,6 +265,16 @@ int pmx_p2plane_system(pmx_ctx* ctx, double* A, double* b, pmx_stats* st);
 /* Point-to-point: mean_p, mean_q (D each, T values), m = sum (qc w) pc^T
  * (D x D row-major, double sums of T products). */
 int pmx_p2point_system(pmx_ctx* ctx, double* mean_p, double* mean_q, double* m, pmx_stats* st);
+/* PointToPointSimilarityErrorMinimizer::compute's sums
+ * (ErrorMinimizers/PointToPointSimilarity.cpp:55-73): mean_p, mean_q and m as
+ * pmx_p2point_system, and *sigma = sum over the kept pairs of ||p - mean_p||^2 w
+ * (:69): each pair's squared norm of the centred step reading point in T,
+ * (x x + y y) + z z, times its weight, summed in double.  The caller forms
+ * scale = (sum of m's singular values, the last negated with a reflection)
+ * / sigma, 1 when sigma < 0.0001 (:82-90).  Several ranks: sigma is reduced in
+ * the moments' exchange, no collective of its own. */
+int pmx_p2point_similarity_system(pmx_ctx* ctx, double* mean_p, double* mean_q, double* m, double* sigma,
+                                  pmx_stats* st);
 /* PointToPlaneWithCovErrorMinimizer::estimateCovariance
  * (ErrorMinimizers/PointToPlaneWithCov.cpp:72-162) for the last pmx_match, its
  * recorded filter chain and its T_iter; callable after pmx_p2plane_system.
@@ -329,7 +347,9 @@ typedef struct pmx_loop_cfg {
     int filter_kind[8];         /* PMX_FILTER_* */
     double filter_p[8][3];      /* maxDist / minDist / factor / ratio / (minRatio, maxRatio, lambda) / eps */
     int minimizer;              /* 0 PointToPlane, 1 PointToPoint, 2 PointToPlane with covariance
-                                   (PointToPlane's iterations; pmx_loop_covariance afterwards) */
+                                   (PointToPlane's iterations; pmx_loop_covariance afterwards),
+                                   3 PointToPointSimilarity (PointToPointSimilarity.cpp:43-98: the step
+                                   scales; T0 and T_iter need not be rigid, ICP.cpp:145-148) */
     int n_checkers;
     int checker_kind[8];        /* PMX_CHECK_* */
     double checker_p[8][3];     /* Counter: max; Differential: rot, trans, smoothLength; Bound: rot, trans */

@@ -154,7 +154,7 @@ EXPORTS = [
     "pmx_outlier_default", "pmx_outlier_null", "pmx_outlier_maxdist", "pmx_outlier_mindist",
     "pmx_outlier_mediandist", "pmx_outlier_trimmed", "pmx_outlier_vartrimmed", "pmx_outlier_robust",
     "pmx_robust_scale", "pmx_set_reading_radii", "pmx_set_reading_normals", "pmx_outlier_surface_normal",
-    "pmx_p2plane_system", "pmx_p2point_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
+    "pmx_p2plane_system", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid",
@@ -201,6 +201,8 @@ def lib():
         l.pmx_p2plane_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         l.pmx_p2point_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(Stats)]
+        l.pmx_p2point_similarity_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(C.c_double), C.POINTER(Stats)]
         l.pmx_p2plane_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         l.pmx_loop_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         l.pmx_get_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -528,6 +530,19 @@ class Context:
         self._chk(self._l.pmx_p2point_system(self.h, _ptr(mp), _ptr(mq), _ptr(m), C.byref(st)))
         return mp, mq, m.reshape(D, D), st
 
+    def p2point_similarity_system(self):
+        """PointToPointSimilarityErrorMinimizer's sums for the last match:
+        (mean_p, mean_q, m, sigma, stats), sigma = sum ||p - mean_p||^2 w."""
+        D = self.rows - 1
+        mp = np.zeros(D)
+        mq = np.zeros(D)
+        m = np.zeros(D * D)
+        sigma = C.c_double()
+        st = Stats()
+        self._chk(self._l.pmx_p2point_similarity_system(self.h, _ptr(mp), _ptr(mq), _ptr(m), C.byref(sigma),
+                                                        C.byref(st)))
+        return mp, mq, m.reshape(D, D), sigma.value, st
+
     def p2plane_covariance(self, T_step):
         """The sums of PointToPlaneWithCovErrorMinimizer's estimate for the last
         match and the solved increment T_step (pmx_p2plane_covariance):
@@ -593,7 +608,8 @@ class Context:
             for j, v in enumerate(p):
                 cfg.filter_p[i][j] = float(v)
         cfg.minimizer = (2 if minimizer.startswith("PointToPlaneWithCov")
-                         else 0 if minimizer.startswith("PointToPlane") else 1)
+                         else 0 if minimizer.startswith("PointToPlane")
+                         else 3 if minimizer.startswith("PointToPointSimilarity") else 1)
         cfg.n_checkers = len(checkers)
         for i, (name, *p) in enumerate(checkers):
             cfg.checker_kind[i] = CHECK_KIND[name]

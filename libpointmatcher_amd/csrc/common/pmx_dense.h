@@ -621,6 +621,48 @@ PMX_HD void p2point_transform(int rows, const T* m, const T* mp, const T* mq, T*
     out[D * rows + D] = 1;
 }
 
+// PointToPointSimilarity: scale R with R = U V^T as above; a reflection is
+// fixed on row D - 1 of V^T and the matching singular value is negated with
+// it; scale = (sum of the singular values) / sigma, 1 when sigma < 0.0001;
+// t = mean_q - scale R mean_p (PointToPointSimilarity.cpp:69-97), all in T
+template <typename T>
+PMX_HD void p2point_similarity_transform(int rows, const T* m, const T* mp, const T* mq, T sigma, T* out) {
+    const int D = rows - 1;
+    T U[9], S[3], V[9], R[9] = {}, Vt[9];
+    jacobi_svd(m, D, U, S, V);
+    for (int r = 0; r < D; ++r)
+        for (int c = 0; c < D; ++c) Vt[r * D + c] = V[c * D + r];
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int r = 0; r < D; ++r)
+            for (int c = 0; c < D; ++c) {
+                T s = 0;
+                for (int k = 0; k < D; ++k) s = s + U[r * D + k] * Vt[k * D + c];
+                R[r * D + c] = s;
+            }
+        const T det = D == 3 ? R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) +
+                                   R[2] * (R[3] * R[7] - R[4] * R[6])
+                             : R[0] * R[3] - R[1] * R[2];
+        if (pass == 1 || !(det < (T)0)) break;
+        for (int c = 0; c < D; ++c) Vt[(D - 1) * D + c] = -Vt[(D - 1) * D + c];
+        S[D - 1] = -S[D - 1];
+    }
+    T ssum = S[0];
+    for (int i = 1; i < D; ++i) ssum = ssum + S[i];
+    T scale = ssum / sigma;
+    if (sigma < (T)0.0001) scale = (T)1;
+    for (int i = 0; i < rows * rows; ++i) out[i] = 0;
+    for (int r = 0; r < D; ++r) {
+        T s = 0;
+        for (int c = 0; c < D; ++c) {
+            const T sr = scale * R[r * D + c];  // (scale * rotMatrix) * meanReading
+            s = s + sr * mp[c];
+            out[r * rows + c] = sr;
+        }
+        out[r * rows + D] = mq[r] - s;
+    }
+    out[D * rows + D] = 1;
+}
+
 // PointToPlaneWithCov: Matrix::inverse() of the 6 x 6 Hessian
 // (PointToPlaneWithCov.cpp:156; Eigen inverts a dynamic matrix by
 // PartialPivLU): LU with row pivoting, then the identity's columns solved.  A

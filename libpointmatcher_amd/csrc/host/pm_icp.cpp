@@ -5,9 +5,9 @@
 //   KDTreeMatcher, KDTreeVarDistMatcher  MatchersImpl.h:74-134
 //   Null/MaxDist/MinDist/MedianDist/TrimmedDist/VarTrimmedDist/Robust OutlierFilter
 //                                 OutlierFiltersImpl.h:51-260
-//   PointToPlane / PointToPlaneWithCov / PointToPoint ErrorMinimizer
+//   PointToPlane / PointToPlaneWithCov / PointToPoint / PointToPointSimilarity ErrorMinimizer
 //                                 ErrorMinimizers/PointToPlane.h:61-90, PointToPlaneWithCov.h:60-86,
-//                                 PointToPoint.h
+//                                 PointToPoint.h, PointToPointSimilarity.h
 //   Counter / Differential / Bound TransformationChecker
 //                                 TransformationCheckersImpl.h:60-130
 //   Identity / SurfaceNormal / MaxDist / MinDist / RandomSampling / FixStepSampling /
@@ -570,6 +570,39 @@ struct PointToPointEM : PM<T>::ErrorMinimizer {
         cfg.minimizer = 1;
         return true;
     }
+};
+
+// PointToPointSimilarityErrorMinimizer (ErrorMinimizers/PointToPointSimilarity.cpp:43-98):
+// PointToPoint's means and moments plus sigma from the device, the SVD, the
+// reflection fix on V^T's row and its singular value, and the scale in T.  No
+// parameters (ADD_TO_REGISTRAR_NO_PARAM).  Statistics and getOverlap() without
+// a "simpleSensorNoise" descriptor are PointToPoint's.
+template <typename T>
+struct PointToPointSimilarityEM : PM<T>::ErrorMinimizer {
+    explicit PointToPointSimilarityEM(const Parametrizable::Parameters&) {
+        this->className = "PointToPointSimilarityErrorMinimizer";
+    }
+    std::vector<T> compute(Device& d, int rows) override {
+        const int D = rows - 1;
+        double mp[3], mq[3], md[9], sigma = 0;
+        pmx_stats st;
+        d.check(pmx_p2point_similarity_system(d.ctx, mp, mq, md, &sigma, &st));
+        this->setStats(st);
+        T m[9], mpT[3], mqT[3];
+        for (int i = 0; i < D * D; ++i) m[i] = (T)md[i];
+        for (int i = 0; i < D; ++i) {
+            mpT[i] = (T)mp[i];
+            mqT[i] = (T)mq[i];
+        }
+        std::vector<T> out((size_t)rows * rows, (T)0);
+        dense::p2point_similarity_transform(rows, m, mpT, mqT, (T)sigma, out.data());  // (shared with the device loop)
+        return out;
+    }
+    bool loopConfig(pmx_loop_cfg& cfg) const override {
+        cfg.minimizer = 3;
+        return true;
+    }
+    bool similarity() const override { return true; }
 };
 
 // ---- transformation checkers ------------------------------------------------
@@ -1244,6 +1277,8 @@ PointMatcher<T>::PointMatcher() {
                                 [](const Ps& p) { return std::make_shared<PointToPlaneWithCovEM<T>>(p); }, true);
     ErrorMinimizerRegistrar.reg("PointToPointErrorMinimizer",
                                 [](const Ps& p) { return std::make_shared<PointToPointEM<T>>(p); }, false);
+    ErrorMinimizerRegistrar.reg("PointToPointSimilarityErrorMinimizer",
+                                [](const Ps& p) { return std::make_shared<PointToPointSimilarityEM<T>>(p); }, false);
     TransformationCheckerRegistrar.reg("CounterTransformationChecker",
                                        [](const Ps& p) { return std::make_shared<CounterTC<T>>(p); }, true);
     TransformationCheckerRegistrar.reg("DifferentialTransformationChecker",
@@ -1490,7 +1525,10 @@ void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const Tra
     for (int r = 0; r < dim - 1; ++r) inv[r * dim + dim - 1] = -T_refIn_refMean_[r * dim + dim - 1];
     T_refMean_dataIn_.assign((size_t)dim * dim, (T)0);
     dense::matmul(inv.data(), T_init.data(), dim, T_refMean_dataIn_.data());
-    if (std::fabs((T)1 - dense::det_rot(T_refMean_dataIn_.data(), dim)) > (T)0.001)
+    // (RigidTransformation::compute's check, TransformationsImpl.cpp:62-63; a
+    // SimilarityTransformation checks nothing, :197-203)
+    if (!similarityTransformation() &&
+        std::fabs((T)1 - dense::det_rot(T_refMean_dataIn_.data(), dim)) > (T)0.001)
         throw TransformationError("RigidTransformation: Error, rotation matrix is not orthogonal.");
     // transformations.apply(reading, T_refMean_dataIn): done on the device
     dev.check(pmx_set_reading(dev.ctx, reading.feat(), dim, reading.n, T_refMean_dataIn_.data()));
@@ -1761,7 +1799,8 @@ bool PointMatcher<T>::ICP::stepModules() {
     // one pass of the loop body, ICP.cpp:371-430
     if (!iterate_) return false;
     const int dim = rows_;
-    if (std::fabs((T)1 - dense::det_rot(T_iter_.data(), dim)) > (T)0.001)  // TransformationsImpl.cpp:62-63
+    if (!similarityTransformation() &&
+        std::fabs((T)1 - dense::det_rot(T_iter_.data(), dim)) > (T)0.001)  // TransformationsImpl.cpp:62-63
         throw TransformationError("RigidTransformation: Error, rotation matrix is not orthogonal.");
     if (!readingStepDataPointsFilters.empty()) {  // ICP.cpp:373-377
         DataPoints stepReading(stepBase_);

@@ -120,6 +120,9 @@ struct PointMatcher {
         virtual ~ErrorMinimizer() {}
         virtual TransformationParameters compute(Device& dev, int rows) = 0;
         virtual bool loopConfig(pmx_loop_cfg&) const { return false; }
+        // the chain holds a SimilarityTransformation instead of a
+        // RigidTransformation (ICP.cpp:145-148: PointToPointSimilarity only)
+        virtual bool similarity() const { return false; }
         // ErrorMinimizer::getCovariance (ErrorMinimizer.cpp:266-270): 6 x 6
         // row-major, zeros unless the minimiser estimates one
         virtual std::vector<T> getCovariance() const { return std::vector<T>(36, (T)0); }
@@ -254,6 +257,11 @@ struct PointMatcher {
         std::vector<TransformationParameters> trace;  // T_iter after each iteration
         bool keepTrace = false;
         bool getMaxNumIterationsReached() const { return maxNumIterationsReached; }
+        // The chain's transformation, chosen as ICP.cpp:145-148 chooses it:
+        // SimilarityTransformation with PointToPointSimilarityErrorMinimizer,
+        // RigidTransformation otherwise.  A similarity checks nothing
+        // (TransformationsImpl.cpp:197-203): T_init and the iterates may scale.
+        bool similarityTransformation() const { return errorMinimizer && errorMinimizer->similarity(); }
 
       private:
         bool stepModules();                   // ICP.cpp:371-430 through the module calls

@@ -1482,8 +1482,12 @@ int p2plane_enqueue(pmx_ctx* c) {
 }
 
 // the point-to-point sums, means and cross-covariance (no host sync);
+// similarity (PointToPointSimilarityErrorMinimizer): the second pass adds
+// sigma behind the moments (d_result[25]); always the two-pass form, whose
+// terms are centred in T before they are squared (sigma from raw sums would
+// cancel), so p2p_onepass does not touch it
 template <typename T>
-int p2point_enqueue(pmx_ctx* c) {
+int p2point_enqueue(pmx_ctx* c, bool similarity) {
     Mat4<T> Tm = step_mat<T>(c);
     WChain<T> chain = chain_of<T>(c);
     if (chain.robust && chain.rb_p2pl) {  // (the point-to-point kernels carry no normals)
@@ -1492,7 +1496,7 @@ int p2point_enqueue(pmx_ctx* c) {
         chain.w_arr = (const T*)c->d_w;
     }
     const GridDesc<T>* gd = (const GridDesc<T>*)c->d_gdesc;
-    if (c->loop_on && c->loop_dev.p2p_onepass) {
+    if (c->loop_on && c->loop_dev.p2p_onepass && !similarity) {
         // device loop: both passes' sums in one read of the matches, the
         // step centres the moments (LoopCfg.p2p_onepass)
         launch_p2point_moments<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists,
@@ -1514,16 +1518,18 @@ int p2point_enqueue(pmx_ctx* c) {
     if (rc) return rc;
     launch_p2point_means<T>(c->d_result, (T*)c->d_means, c->dim, loop_ctl(c), c->stream);
     launch_p2point_pass2<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists, c->d_ids,
-                            chain, c->knn, c->N, (const T*)c->d_means, c->d_partials, loop_ctl(c), gd, c->stream);
+                            chain, c->knn, c->N, (const T*)c->d_means, c->d_partials, loop_ctl(c), gd, c->stream,
+                            similarity);
+    const int nv2 = similarity ? 10 : 9;  // (sigma rides in the moments' exchange: no extra collective)
     if (c->fuse_final) {  // (summed by the fused finalize + step launch)
         c->final_out = c->d_result + 16;
-        c->final_nv = 9;
+        c->final_nv = nv2;
         HIPCHK(c, hipGetLastError());
         return PMX_OK;
     }
-    launch_finalize(c->d_partials, kRedBlocks, 9, c->d_result + 16, loop_ctl(c), c->stream);
+    launch_finalize(c->d_partials, kRedBlocks, nv2, c->d_result + 16, loop_ctl(c), c->stream);
     HIPCHK(c, hipGetLastError());
-    return allreduce_f64(c, c->d_result + 16, 9);
+    return allreduce_f64(c, c->d_result + 16, nv2);
 }
 
 template <typename T>
@@ -1562,10 +1568,10 @@ int p2plane_impl(pmx_ctx* c, double* A, double* b, pmx_stats* st) {
 }
 
 template <typename T>
-int p2point_impl(pmx_ctx* c, double* mean_p, double* mean_q, double* m, pmx_stats* st) {
+int p2point_impl(pmx_ctx* c, double* mean_p, double* mean_q, double* m, pmx_stats* st, double* sigma = nullptr) {
     int rc = check_match(c);
     if (rc) return rc;
-    if ((rc = p2point_enqueue<T>(c))) return rc;
+    if ((rc = p2point_enqueue<T>(c, sigma != nullptr))) return rc;
     if ((rc = readback(c))) return rc;
     after_readback(c);
     const double* r = c->h_result;
@@ -1587,6 +1593,7 @@ int p2point_impl(pmx_ctx* c, double* mean_p, double* mean_q, double* m, pmx_stat
     }
     for (int i = 0; i < D; ++i)
         for (int j = 0; j < D; ++j) m[i * D + j] = r[16 + i * 3 + j];
+    if (sigma) *sigma = r[25];
     return PMX_OK;
 }
 
@@ -1688,7 +1695,7 @@ int get_weights_impl(pmx_ctx* c, void* w) {
     template int outlier_impl<T>(pmx_ctx*, int, int, double, double, double);               \
     template int outlier_robust_impl<T>(pmx_ctx*, int, int, double, double, int, double, int); \
     template int p2plane_enqueue<T>(pmx_ctx*);                                              \
-    template int p2point_enqueue<T>(pmx_ctx*);                                              \
+    template int p2point_enqueue<T>(pmx_ctx*, bool);                                        \
     template int p2plane_cov_impl<T>(pmx_ctx*, const T*, double*, double*, int64_t*);       \
     template int get_matches_impl<T>(pmx_ctx*, void*, int32_t*);                            \
     template int unpermute<T>(pmx_ctx*, const std::vector<T>&, T*, int);
@@ -1787,6 +1794,11 @@ int pmx_p2plane_covariance(pmx_ctx* c, const void* T_step, double* H, double* Q,
 int pmx_p2point_system(pmx_ctx* c, double* mp, double* mq, double* m, pmx_stats* st) {
     if (!c || !mp || !mq || !m) return fail(c, PMX_E_BAD_PARAM, "null argument");
     return DISPATCH(c, p2point_impl<float>(c, mp, mq, m, st), p2point_impl<double>(c, mp, mq, m, st));
+}
+
+int pmx_p2point_similarity_system(pmx_ctx* c, double* mp, double* mq, double* m, double* sigma, pmx_stats* st) {
+    if (!c || !mp || !mq || !m || !sigma) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    return DISPATCH(c, p2point_impl<float>(c, mp, mq, m, st, sigma), p2point_impl<double>(c, mp, mq, m, st, sigma));
 }
 
 int pmx_get_matches(pmx_ctx* c, void* dists, int32_t* ids) {

@@ -418,8 +418,9 @@ int outlier_robust_impl(pmx_ctx* c, int pos, int fct, double tuning, double appr
                         int p2pl);
 template <typename T>
 int p2plane_enqueue(pmx_ctx* c);
+// similarity: PointToPointSimilarity's sums (sigma after the moments, two passes always)
 template <typename T>
-int p2point_enqueue(pmx_ctx* c);
+int p2point_enqueue(pmx_ctx* c, bool similarity = false);
 template <typename T>
 int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* pairs);
 template <typename T>

@@ -533,10 +533,12 @@ template <typename T>
 void launch_p2point_moments(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
                             const WChain<T>& chain, int k, int64_t N, double* partials, const LoopCtl* ctl,
                             const GridDesc<T>* gd, hipStream_t s);
+// similarity (PointToPointSimilarity): a tenth sum, sigma (pmx_reduce.hip)
 template <typename T>
 void launch_p2point_pass2(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d,
                           const int32_t* ids, const WChain<T>& chain, int k, int64_t N, const T* means_dev,
-                          double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s);
+                          double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s,
+                          bool similarity = false);
 template <typename T>
 void launch_weights_chain(const T* d, T* w, int64_t n, const WChain<T>& chain, const P4<T>* rd, const Mat4<T>& Tm,
                           const P4<T>* ref, const P4<T>* nrm, int rs, const int32_t* ids, int k, hipStream_t s);

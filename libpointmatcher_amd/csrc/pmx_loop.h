@@ -16,7 +16,8 @@ constexpr int kMaxLevels = 8;
 constexpr int kDiagCap = 1024;
 constexpr int kDiagWords = 4;
 // doubles of the iteration block the step reads (point-to-plane: <= 36 + 6 +
-// 5 in the full layout; point-to-point: the second pass at 16..24)
+// 5 in the full layout; point-to-point: the second pass at 16..24, the
+// similarity minimiser's sigma at 25)
 constexpr int kStepRes = 48;
 
 enum CheckKind { kCheckCounter = 0, kCheckDifferential = 1, kCheckBound = 2 };
@@ -25,7 +26,7 @@ enum LoopReason { kLoopRunning = 0, kLoopCounter = 1, kLoopDifferential = 2, kLo
 // device-side error codes (mapped to pmx.h codes / messages by the host)
 enum LoopErr {
     kLoopNoPoints = -1,   // PMX_E_NO_POINTS: "ErrorMnimizer: no point to minimize"
-    kLoopNotRigid = -4,   // PMX_E_TRANSFORMATION
+    kLoopNotRigid = -4,   // PMX_E_TRANSFORMATION (never with the similarity minimiser)
     kLoopRotNaN = -20,    // ConvergenceError("abs rotation norm not a number")
     kLoopTransNaN = -21,  // ConvergenceError("abs translation norm not a number")
     kLoopBound = -22,     // ConvergenceError("limit out of bounds ...")
@@ -37,7 +38,7 @@ struct Mat4d {
 
 struct LoopCfg {
     int rows;       // 3 (2-D) or 4 (3-D)
-    int minimizer;  // 0 point-to-plane, 1 point-to-point
+    int minimizer;  // 0 point-to-plane, 1 point-to-point, 2 point-to-point similarity (pmx_loop_cfg.minimizer 3)
     int full;       // point-to-plane: the weighted reduction's layout (full A; a RobustOutlierFilter chain)
     int n_checkers;
     int checker_kind[kMaxCheckers];

@@ -10,7 +10,9 @@
 //   * quantile / empty-match errors of the iteration (ConvergenceError),
 //   * PointToPlane: solvePossiblyUnderdetermined on the 6x6 / 3x3 system and
 //     the rigid step (PointToPlane.cpp:108-161, 245-312); PointToPoint: the
-//     SVD of the cross-covariance (PointToPoint.cpp:61-101),
+//     SVD of the cross-covariance (PointToPoint.cpp:61-101);
+//     PointToPointSimilarity: the same SVD and the scale
+//     (PointToPointSimilarity.cpp:43-98), a step that is not rigid,
 //   * T_iter = dT * T_iter (ICP.cpp:419),
 //   * the checkers in chain order: Counter, Differential, Bound
 //     (TransformationCheckersImpl.cpp:45-225), with the reference's stop /
@@ -154,13 +156,17 @@ void launch_finalize_step(const double* partials, int nblocks, int nv, double* o
     if (cfg.rows == 4) {
         if (cfg.minimizer == 0)
             PMX_FSTEP(4, 0);
-        else
+        else if (cfg.minimizer == 1)
             PMX_FSTEP(4, 1);
+        else
+            PMX_FSTEP(4, 2);
     } else {
         if (cfg.minimizer == 0)
             PMX_FSTEP(3, 0);
-        else
+        else if (cfg.minimizer == 1)
             PMX_FSTEP(3, 1);
+        else
+            PMX_FSTEP(3, 2);
     }
 #undef PMX_FSTEP
 }
@@ -229,13 +235,17 @@ void launch_loop_step(LoopCtl* ctl, LoopState<T>* S, const double* res, const in
     if (cfg.rows == 4) {
         if (cfg.minimizer == 0)
             PMX_STEP(4, 0);
-        else
+        else if (cfg.minimizer == 1)
             PMX_STEP(4, 1);
+        else
+            PMX_STEP(4, 2);
     } else {
         if (cfg.minimizer == 0)
             PMX_STEP(3, 0);
-        else
+        else if (cfg.minimizer == 1)
             PMX_STEP(3, 1);
+        else
+            PMX_STEP(3, 2);
     }
 #undef PMX_STEP
 }

@@ -34,6 +34,11 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     pmx_loop_cfg cfg_pl = *cfg_in;
     const bool with_cov = cfg_in->minimizer == 2;
     if (with_cov) cfg_pl.minimizer = 0;
+    // minimizer 3 (PointToPointSimilarityErrorMinimizer) runs PointToPoint's
+    // reductions with sigma added to the second pass; its step (LoopCfg
+    // minimizer 2) scales, and T_iter is not held to be rigid
+    const bool similarity = cfg_in->minimizer == 3;
+    if (similarity) cfg_pl.minimizer = 1;
     const pmx_loop_cfg* cfg = &cfg_pl;
     if (!c->d_ref) return fail(c, PMX_E_STATE, "no reference (Matcher::init not called)");
     if (!c->d_rd && c->N > 0) return fail(c, PMX_E_STATE, "no reading");
@@ -85,7 +90,7 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     if (c->levels.size() > (size_t)kMaxLevels) return fail(c, PMX_E_BAD_PARAM, "device loop: at most 8 grid levels");
     LoopCfg d{};
     d.rows = c->rows;
-    d.minimizer = cfg->minimizer;
+    d.minimizer = similarity ? 2 : cfg->minimizer;
     d.full = n_robust > 0 ? 1 : 0;  // (point-to-plane: the weighted system's full A layout)
     d.n_checkers = cfg->n_checkers;
     for (int i = 0; i < cfg->n_checkers; ++i) {
@@ -112,7 +117,8 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     // and the one-pass form drifted 1.05e-5 from the per-module path over 25
     // iterations, past the 1e-5 bar; in double both are far inside 1e-12)
     d.keep_increment = with_cov ? 1 : 0;
-    d.p2p_onepass = cfg->minimizer == 1 && c->p2p_onepass && c->dtype == PMX_F64 ? 1 : 0;
+    // (never with similarity: sigma from raw sums would cancel; two passes in both dtypes)
+    d.p2p_onepass = cfg->minimizer == 1 && !similarity && c->p2p_onepass && c->dtype == PMX_F64 ? 1 : 0;
     int rc;
     size_t cap = 0;
     (void)cap;  // (LoopState lives in the status block)
@@ -278,7 +284,7 @@ int loop_enqueue_iteration(pmx_ctx* c) {
     // one rank: the minimiser's last finalize and the step in one launch
     c->fuse_final = fuse_env && !sharded(c);
     c->final_out = nullptr;
-    rc = cfg.minimizer == 0 ? p2plane_enqueue<T>(c) : p2point_enqueue<T>(c);
+    rc = cfg.minimizer == 0 ? p2plane_enqueue<T>(c) : p2point_enqueue<T>(c, c->loop_dev.minimizer == 2);
     const bool fused = c->fuse_final && c->final_out;
     c->fuse_final = false;
     const bool step_counter = c->step_counter;

@@ -1,4 +1,7 @@
-// pmx_match.hip — exact brute-force k-NN with the rigid transform fused in.
+// pmx_match.hip — exact brute-force k-NN with the iteration's transform fused in
+// (rigid, or any affine matrix: PointToPointSimilarity's iterates scale, and
+// SimilarityTransformation::compute applies `parameters * features` alike,
+// TransformationsImpl.cpp:177).
 //
 // Replaces KDTreeMatcher::findClosests (pointmatcher/MatchersImpl.cpp:85-101,
 // libnabo knn [ext]) and the per-iteration transformations.apply of

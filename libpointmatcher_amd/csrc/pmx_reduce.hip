@@ -290,8 +290,11 @@ void launch_p2point_means(const double* sums, T* means_dev, int dim, const LoopC
 }
 
 // pass 2: m = sum (qc * w) pc^T  (PointToPoint.cpp:76-81), 3x3 (2-D uses the
-// top-left 2x2; z terms are exactly zero)
-template <typename T, bool SN>
+// top-left 2x2; z terms are exactly zero).  SIM (PointToPointSimilarity): a
+// tenth sum, sigma = sum ||pc||^2 w (PointToPointSimilarity.cpp:69): each
+// pair's squared norm in T, (pcx pcx + pcy pcy) + pcz pcz, times w, added in
+// fp64.  The rigid minimiser's instantiations (SIM false) hold nine sums as before.
+template <typename T, bool SN, bool SIM>
 __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                             const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                             const int32_t* __restrict__ ids, WChain<T> chain, int k,
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
                                                             double* __restrict__ partials,
                                                             const LoopCtl* __restrict__ ctl,
                                                             const GridDesc<T>* __restrict__ gd) {
-    constexpr int NV = 9;
+    constexpr int NV = SIM ? 10 : 9;
     if (ctl) {  // device loop
         if (ctl->done) return;
         ctl_transform(ctl, Tm);
@@ -336,6 +339,7 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
 #pragma unroll
                 for (int c = 0; c < 3; ++c) acc[r * 3 + c] += (double)((qc[r] * w) * pc[c]);  // (qc * w) pc
             }
+            if constexpr (SIM) acc[9] += (double)(((pc[0] * pc[0] + pc[1] * pc[1]) + pc[2] * pc[2]) * w);
         }
     }
     block_store<NV>(acc, partials);
@@ -344,8 +348,9 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
 template <typename T>
 void launch_p2point_pass2(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
                           const WChain<T>& chain, int k, int64_t N, const T* means_dev, double* partials,
-                          const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s) {
-    auto* const kern = chain.sn.rn ? p2point_pass2_kernel<T, true> : p2point_pass2_kernel<T, false>;
+                          const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s, bool similarity) {
+    auto* const kern = similarity ? (chain.sn.rn ? p2point_pass2_kernel<T, true, true> : p2point_pass2_kernel<T, false, true>)
+                                  : (chain.sn.rn ? p2point_pass2_kernel<T, true, false> : p2point_pass2_kernel<T, false, false>);
     hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N, means_dev, partials,
                        ctl, gd);
 }
@@ -475,7 +480,7 @@ void launch_weights_chain(const T* d, T* w, int64_t n, const WChain<T>& chain, c
                                             const GridDesc<T>*, hipStream_t);                                      \
     template void launch_p2point_pass2<T>(const P4<T>*, const Mat4<T>&, const P4<T>*, const T*, const int32_t*,     \
                                           const WChain<T>&, int, int64_t, const T*, double*, const LoopCtl*,         \
-                                          const GridDesc<T>*, hipStream_t);                                          \
+                                          const GridDesc<T>*, hipStream_t, bool);                                    \
     template void launch_weights_chain<T>(const T*, T*, int64_t, const WChain<T>&, const P4<T>*, const Mat4<T>&,     \
                                           const P4<T>*, const P4<T>*, int, const int32_t*, int, hipStream_t);
 PMX_INST(float)

@@ -3,7 +3,9 @@
 //   * quantile / empty-match errors of the iteration (ConvergenceError),
 //   * PointToPlane: solvePossiblyUnderdetermined on the 6x6 / 3x3 system and
 //     the rigid step (PointToPlane.cpp:108-161, 245-312); PointToPoint: the
-//     SVD of the cross-covariance (PointToPoint.cpp:61-101),
+//     SVD of the cross-covariance (PointToPoint.cpp:61-101);
+//     PointToPointSimilarity: the same SVD and the scale
+//     (PointToPointSimilarity.cpp:43-98), a step that is not rigid,
 //   * T_iter = dT * T_iter (ICP.cpp:419),
 //   * the checkers in chain order: Counter, Differential, Bound
 //     (TransformationCheckersImpl.cpp:45-225), with the reference's stop /
@@ -132,8 +134,9 @@ __device__ __forceinline__ bool well_conditioned(const T* A, const T* L) {
 // ROWS is the homogeneous dimension (4 in 3-D, 3 in 2-D): with every size a
 // compile-time constant the dense kit's arrays live in VGPRs, not scratch
 // (a single lane walking scratch took ~75 us per iteration at C3).
-// MIN: the minimiser (0 point-to-plane, 1 point-to-point) as a template
-// parameter, so each kernel holds one minimiser's dense code (registers).
+// MIN: the minimiser (0 point-to-plane, 1 point-to-point, 2 point-to-point
+// similarity) as a template parameter, so each kernel holds one minimiser's
+// dense code (registers).
 template <typename T, int ROWS, int MIN>
 __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T>* __restrict__ S,
                                        const double* __restrict__ res, int e, unsigned long long vis0,
@@ -190,7 +193,17 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
     S->touched += vis0;
     // the step transform
     T dT[16];
-    if constexpr (MIN == 0) {
+    if constexpr (MIN == 2) {
+        // PointToPointSimilarity: the two passes' means and moments, sigma
+        // behind them (p2point_enqueue); p2p_onepass is the rigid minimiser's
+        T m[9], mp[3], mq[3];
+        for (int i = 0; i < D; ++i) {
+            mp[i] = means[i];
+            mq[i] = means[3 + i];
+            for (int j = 0; j < D; ++j) m[i * D + j] = (T)res[16 + i * 3 + j];
+        }
+        p2point_similarity_transform(rows, m, mp, mq, (T)res[25], dT);
+    } else if constexpr (MIN == 0) {
         constexpr int NF = D == 3 ? 6 : 3;
         T A[NF * NF], b[NF], x[NF], L[NF * NF];
         if (cfg.full) {  // (a robust chain: (w F_r) F_c in T, the reference's asymmetric wF * F^T)
@@ -335,8 +348,9 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
         return;
     }
     // the next step starts with RigidTransformation::compute's check
-    // (TransformationsImpl.cpp:62-63)
-    if (fabs((T)1 - det_rot(Tit, rows)) > (T)0.001) {
+    // (TransformationsImpl.cpp:62-63); the similarity minimiser's chain holds
+    // a SimilarityTransformation, which checks nothing (:197-203)
+    if (MIN != 2 && fabs((T)1 - det_rot(Tit, rows)) > (T)0.001) {
         loop_fail(ctl, S, kLoopNotRigid, kLoopError);
         return;
     }
