@@ -1,5 +1,102 @@
 """Shared test helpers (test infrastructure)."""
+import atexit
+import ctypes
+import os
+import shutil
+import subprocess
+import tempfile
+
 import numpy as np
+
+TESTS = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(TESTS)
+
+
+class DenseKit:
+    """The host form of csrc/common/pmx_dense.h (tests/dense_shim.cpp, plain
+    C++: what the per-module path runs) through ctypes.  Arrays go in and come
+    out in `dtype` (float32 / float64), row-major."""
+
+    def __init__(self, lib):
+        self._l = lib
+
+    def _f(self, name, dtype):
+        return getattr(self._l, f"pmd_{name}_" + ("f32" if np.dtype(dtype) == np.float32 else "f64"))
+
+    @staticmethod
+    def _p(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    def solve_underdetermined(self, A, b, dtype):
+        A = np.ascontiguousarray(A, dtype=dtype)
+        b = np.ascontiguousarray(b, dtype=dtype)
+        x = np.zeros(len(b), dtype)
+        self._f("solve_underdetermined", dtype)(self._p(A), self._p(b), len(b), self._p(x))
+        return x
+
+    def qr_rank(self, A, dtype):
+        A = np.ascontiguousarray(A, dtype=dtype)
+        return int(self._f("qr_rank", dtype)(self._p(A), A.shape[0]))
+
+    def p2plane_transform(self, x, rows, dtype):
+        x = np.ascontiguousarray(x, dtype=dtype)
+        out = np.zeros((rows, rows), dtype)
+        self._f("p2plane_transform", dtype)(rows, self._p(x), self._p(out))
+        return out
+
+    def p2plane_step(self, A, b, rows, dtype):
+        """solve + increment, the step of PointToPlaneErrorMinimizer: (dT, x)."""
+        x = self.solve_underdetermined(A, b, dtype)
+        return self.p2plane_transform(x, rows, dtype), x
+
+    def p2point_transform(self, m, mp, mq, dtype):
+        m = np.ascontiguousarray(m, dtype=dtype)
+        D = m.shape[0]
+        mp = np.ascontiguousarray(mp, dtype=dtype)
+        mq = np.ascontiguousarray(mq, dtype=dtype)
+        out = np.zeros((D + 1, D + 1), dtype)
+        self._f("p2point_transform", dtype)(D + 1, self._p(m), self._p(mp), self._p(mq), self._p(out))
+        return out
+
+    def p2point_similarity_transform(self, m, mp, mq, sigma, dtype):
+        m = np.ascontiguousarray(m, dtype=dtype)
+        D = m.shape[0]
+        mp = np.ascontiguousarray(mp, dtype=dtype)
+        mq = np.ascontiguousarray(mq, dtype=dtype)
+        out = np.zeros((D + 1, D + 1), dtype)
+        sc = ctypes.c_float if np.dtype(dtype) == np.float32 else ctypes.c_double
+        self._f("p2point_similarity_transform", dtype)(D + 1, self._p(m), self._p(mp), self._p(mq),
+                                                       sc(float(np.dtype(dtype).type(sigma))), self._p(out))
+        return out
+
+    def jacobi_svd(self, A, dtype):
+        """(U, S, V, nonzero singular values): A = U diag(S) V^T, S descending."""
+        A = np.ascontiguousarray(A, dtype=dtype)
+        n = A.shape[0]
+        U, S, V = np.zeros((n, n), dtype), np.zeros(n, dtype), np.zeros((n, n), dtype)
+        nz = self._f("jacobi_svd", dtype)(self._p(A), n, self._p(U), self._p(S), self._p(V))
+        return U, S, V, int(nz)
+
+
+_dense_kit = None
+
+
+def dense_kit():
+    """Build tests/dense_shim.cpp into a temporary directory (once per process)
+    and load it.  Raises FileNotFoundError without g++."""
+    global _dense_kit
+    if _dense_kit is None:
+        cxx = shutil.which("g++")
+        if cxx is None:
+            raise FileNotFoundError("g++")
+        tmp = tempfile.mkdtemp(prefix="pmx_dense_shim_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        so = os.path.join(tmp, "libdense_shim.so")
+        subprocess.check_call([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
+                               "-I", os.path.join(ROOT, "libpointmatcher_amd", "csrc"),
+                               os.path.join(TESTS, "dense_shim.cpp"), "-o", so])
+        _dense_kit = DenseKit(ctypes.CDLL(so))
+    return _dense_kit
 
 
 def hom(a, dtype=None):
