@@ -1408,14 +1408,13 @@ double host_limit(const pmx_ctx* c) {
     return v;
 }
 
-void fill_stats(const pmx_ctx* c, pmx_stats* st, double kept, double nz, double rm, double rp, double sw,
-                double limit) {
+void fill_stats(const pmx_ctx* c, pmx_stats* st, const SumStats& s, double limit) {
     if (!st) return;
-    st->kept = (int64_t)kept;
-    st->nonzero_weights = (int64_t)nz;
-    st->rejected_matches = (int64_t)rm;
-    st->rejected_points = (int64_t)rp;
-    st->sum_w = sw;
+    st->kept = (int64_t)s.kept;
+    st->nonzero_weights = (int64_t)s.nz;
+    st->rejected_matches = (int64_t)s.rejM;
+    st->rejected_points = (int64_t)s.rejP;
+    st->sum_w = s.sw;
     st->limit = limit;
     st->n_total = c->N_total * c->knn;
     unsigned long long v = 0;
@@ -1456,11 +1455,17 @@ int materialise_weights(pmx_ctx* c) {
     return PMX_OK;
 }
 
-// the point-to-plane system into the iteration block (no host sync)
+// an enqueue's last reduction summed outside the fused launch: the blocks' partials, then the ranks'
+int finish_sums(pmx_ctx* c, const PendingSums& p) {
+    launch_finalize(c->d_partials, kRedBlocks, p.nv, p.out, loop_ctl(c), c->stream);
+    HIPCHK(c, hipGetLastError());
+    return allreduce_f64(c, p.out, p.nv);
+}
+
+// the point-to-plane system's partials (no host sync; *last: its sum, pmx_ctx.h)
 template <typename T>
-int p2plane_enqueue(pmx_ctx* c) {
+int p2plane_enqueue(pmx_ctx* c, PendingSums* last) {
     const WChain<T> chain = chain_of<T>(c);
-    const int NV = chain.robust ? p2plane_nv_full(c->dim) : p2plane_nv(c->dim);
     Mat4<T> Tm = step_mat<T>(c);
     // (k = 1 after a match that left its neighbour records with normals:
     // the reduction reads them in slot order instead of gathering by id)
@@ -1470,29 +1475,24 @@ int p2plane_enqueue(pmx_ctx* c) {
                               loop_ctl(c), (const GridDesc<T>*)c->d_gdesc, c->vpart_dirty ? c->d_vpart : nullptr,
                               c->stream, nbr ? (const P4<T>*)c->d_nbr : nullptr);
     c->vpart_dirty = false;
-    if (c->fuse_final) {  // (summed by the fused finalize + step launch)
-        c->final_out = c->d_result;
-        c->final_nv = NV;
-        HIPCHK(c, hipGetLastError());
-        return PMX_OK;
-    }
-    launch_finalize(c->d_partials, kRedBlocks, NV, c->d_result, loop_ctl(c), c->stream);
     HIPCHK(c, hipGetLastError());
-    return allreduce_f64(c, c->d_result, NV);
+    *last = {c->d_result, p2plane_nv(c->dim, chain.robust)};
+    return PMX_OK;
 }
 
-// the point-to-point sums, means and cross-covariance (no host sync);
-// similarity (PointToPointSimilarityErrorMinimizer): the second pass adds
-// sigma behind the moments (d_result[25]); always the two-pass form, whose
-// terms are centred in T before they are squared (sigma from raw sums would
-// cancel), so p2p_onepass does not touch it
+// the point-to-point sums, means and cross-covariance (no host sync; *last:
+// the last pass's sum); similarity (PointToPointSimilarityErrorMinimizer): the
+// second pass adds sigma behind the moments (P2PointSums::kSigma); always the
+// two-pass form, whose terms are centred in T before they are squared (sigma
+// from raw sums would cancel), so p2p_onepass does not touch it
 template <typename T>
-int p2point_enqueue(pmx_ctx* c, bool similarity) {
+int p2point_enqueue(pmx_ctx* c, bool similarity, PendingSums* last) {
+    using L = P2PointSums;
     Mat4<T> Tm = step_mat<T>(c);
     WChain<T> chain = chain_of<T>(c);
+    int rc;
     if (chain.robust && chain.rb_p2pl) {  // (the point-to-point kernels carry no normals)
-        const int rc = materialise_weights<T>(c);
-        if (rc) return rc;
+        if ((rc = materialise_weights<T>(c))) return rc;
         chain.w_arr = (const T*)c->d_w;
     }
     const GridDesc<T>* gd = (const GridDesc<T>*)c->d_gdesc;
@@ -1501,35 +1501,34 @@ int p2point_enqueue(pmx_ctx* c, bool similarity) {
         // step centres the moments (LoopCfg.p2p_onepass)
         launch_p2point_moments<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists,
                                   c->d_ids, chain, c->knn, c->N, c->d_partials, loop_ctl(c), gd, c->stream);
-        if (c->fuse_final) {  // (summed by the fused finalize + step launch)
-            c->final_out = c->d_result;
-            c->final_nv = 20;
-            HIPCHK(c, hipGetLastError());
-            return PMX_OK;
-        }
-        launch_finalize(c->d_partials, kRedBlocks, 20, c->d_result, loop_ctl(c), c->stream);
         HIPCHK(c, hipGetLastError());
-        return allreduce_f64(c, c->d_result, 20);
+        *last = {c->d_result, L::kMomentsNV};
+        return PMX_OK;
     }
     launch_p2point_pass1<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists, c->d_ids,
                             chain, c->knn, c->N, c->d_partials, loop_ctl(c), gd, c->stream);
-    launch_finalize(c->d_partials, kRedBlocks, 11, c->d_result, loop_ctl(c), c->stream);
-    int rc = allreduce_f64(c, c->d_result, 11);
-    if (rc) return rc;
+    if ((rc = finish_sums(c, {c->d_result, L::kPass1NV}))) return rc;
     launch_p2point_means<T>(c->d_result, (T*)c->d_means, c->dim, loop_ctl(c), c->stream);
     launch_p2point_pass2<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists, c->d_ids,
                             chain, c->knn, c->N, (const T*)c->d_means, c->d_partials, loop_ctl(c), gd, c->stream,
                             similarity);
-    const int nv2 = similarity ? 10 : 9;  // (sigma rides in the moments' exchange: no extra collective)
-    if (c->fuse_final) {  // (summed by the fused finalize + step launch)
-        c->final_out = c->d_result + 16;
-        c->final_nv = nv2;
-        HIPCHK(c, hipGetLastError());
-        return PMX_OK;
-    }
-    launch_finalize(c->d_partials, kRedBlocks, nv2, c->d_result + 16, loop_ctl(c), c->stream);
     HIPCHK(c, hipGetLastError());
-    return allreduce_f64(c, c->d_result + 16, nv2);
+    // (sigma rides in the moments' exchange: no extra collective)
+    *last = {c->d_result + L::kPass2At, similarity ? L::kPass2SimNV : L::kPass2NV};
+    return PMX_OK;
+}
+
+// after the module path's readback: the iteration's error word, an empty ErrorElements
+int check_minimised(pmx_ctx* c, const SumStats& s) {
+    const int ierr = host_iter_err(c);
+    if (ierr == PMX_E_EMPTY_QUANTILE) return fail(c, PMX_E_EMPTY_QUANTILE, "no outlier to filter");
+    if (ierr == kSelTimeout) {
+        (void)select_reset(c);
+        return fail(c, PMX_E_HIP, "radix select: device wait timed out");
+    }
+    if (ierr) return fail(c, ierr, "quantile must be between 0 and 1");
+    if (s.nz == 0.0 || s.kept == 0.0) return fail(c, PMX_E_NO_POINTS, "ErrorMnimizer: no point to minimize");
+    return PMX_OK;
 }
 
 template <typename T>
@@ -1538,52 +1537,38 @@ int p2plane_impl(pmx_ctx* c, double* A, double* b, pmx_stats* st) {
     if (rc) return rc;
     if (!c->has_normals)
         return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer requires \"normals\" on the reference");
-    const int NF = c->dim == 3 ? 6 : 3;
     const bool full = c->rb_pos >= 0 && c->rb_pos < c->chain_n;  // (the weighted layout, see p2plane_enqueue)
-    const int NS = full ? NF * NF : NF * (NF + 1) / 2;
-    if ((rc = p2plane_enqueue<T>(c))) return rc;
+    PendingSums last;
+    if ((rc = p2plane_enqueue<T>(c, &last))) return rc;
+    if ((rc = finish_sums(c, last))) return rc;
     if ((rc = readback(c))) return rc;
     after_readback(c);
     const double* r = c->h_result;
-    const int ierr = host_iter_err(c);
-    const int o = NS + NF;
-    fill_stats(c, st, r[o + 0], r[o + 1], r[o + 2], r[o + 3], r[o + 4], module_limit(c));
-    if (ierr == PMX_E_EMPTY_QUANTILE) return fail(c, PMX_E_EMPTY_QUANTILE, "no outlier to filter");
-    if (ierr == kSelTimeout) {
-        (void)select_reset(c);
-        return fail(c, PMX_E_HIP, "radix select: device wait timed out");
-    }
-    if (ierr) return fail(c, ierr, "quantile must be between 0 and 1");
-    if (r[o + 1] == 0.0) return fail(c, PMX_E_NO_POINTS, "ErrorMnimizer: no point to minimize");
-    if (r[o + 0] == 0.0) return fail(c, PMX_E_NO_POINTS, "ErrorMnimizer: no point to minimize");
-    if (full) {
-        for (int i = 0; i < NF * NF; ++i) A[i] = r[i];
-    } else {  // mirror the upper triangle (exactly symmetric with 0/1 weights, see pmx_reduce.hip)
-        int a = 0;
-        for (int i = 0; i < NF; ++i)
-            for (int j = i; j < NF; ++j, ++a) A[i * NF + j] = A[j * NF + i] = r[a];
-    }
-    for (int i = 0; i < NF; ++i) b[i] = -r[NS + i];
+    const SumStats s = c->dim == 3 ? p2plane_stats<3>(r, full) : p2plane_stats<2>(r, full);
+    fill_stats(c, st, s, module_limit(c));
+    if ((rc = check_minimised(c, s))) return rc;
+    // (the triangle mirrored: exactly symmetric with 0/1 weights, see pmx_reduce.hip)
+    if (c->dim == 3)
+        full ? p2plane_unpack<double, 3, true>(r, A, b) : p2plane_unpack<double, 3, false>(r, A, b);
+    else
+        full ? p2plane_unpack<double, 2, true>(r, A, b) : p2plane_unpack<double, 2, false>(r, A, b);
     return PMX_OK;
 }
 
 template <typename T>
 int p2point_impl(pmx_ctx* c, double* mean_p, double* mean_q, double* m, pmx_stats* st, double* sigma = nullptr) {
+    using L = P2PointSums;
     int rc = check_match(c);
     if (rc) return rc;
-    if ((rc = p2point_enqueue<T>(c, sigma != nullptr))) return rc;
+    PendingSums last;
+    if ((rc = p2point_enqueue<T>(c, sigma != nullptr, &last))) return rc;
+    if ((rc = finish_sums(c, last))) return rc;
     if ((rc = readback(c))) return rc;
     after_readback(c);
     const double* r = c->h_result;
-    const int ierr = host_iter_err(c);
-    fill_stats(c, st, r[7], r[8], r[9], r[10], r[0], module_limit(c));
-    if (ierr == PMX_E_EMPTY_QUANTILE) return fail(c, PMX_E_EMPTY_QUANTILE, "no outlier to filter");
-    if (ierr == kSelTimeout) {
-        (void)select_reset(c);
-        return fail(c, PMX_E_HIP, "radix select: device wait timed out");
-    }
-    if (ierr) return fail(c, ierr, "quantile must be between 0 and 1");
-    if (r[8] == 0.0 || r[7] == 0.0) return fail(c, PMX_E_NO_POINTS, "ErrorMnimizer: no point to minimize");
+    const SumStats s = p2point_stats(r);
+    fill_stats(c, st, s, module_limit(c));
+    if ((rc = check_minimised(c, s))) return rc;
     T means[6];
     std::memcpy(means, (const char*)c->h_result + kBlkMeans, sizeof(T) * 6);
     const int D = c->dim;
@@ -1592,8 +1577,8 @@ int p2point_impl(pmx_ctx* c, double* mean_p, double* mean_q, double* m, pmx_stat
         mean_q[i] = (double)means[3 + i];
     }
     for (int i = 0; i < D; ++i)
-        for (int j = 0; j < D; ++j) m[i * D + j] = r[16 + i * 3 + j];
-    if (sigma) *sigma = r[25];
+        for (int j = 0; j < D; ++j) m[i * D + j] = r[L::kPass2At + L::moment(i, j)];
+    if (sigma) *sigma = r[L::kSigma];
     return PMX_OK;
 }
 
@@ -1620,16 +1605,13 @@ int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* p
     const bool nbr = nbr_with_normals(c) && !chain.robust;  // (the records p2plane_enqueue reads)
     // the second half of the iteration block's result area: the step's
     // system and the statistics in the first half stay as the minimiser left them
-    double* out = c->d_result + 64;
-    static_assert(64 + kCovNV <= 128 && kCovNV <= kNVMax, "iteration block layout");
+    const PendingSums cov = {c->d_result + kCovAt, kCovNV};
     launch_p2plane_cov<T>((const P4<T>*)c->d_rd, step_mat<T>(c), (const P4<T>*)match_pn(c),
                           (const P4<T>*)match_nrm(c), match_rs(c), (const T*)c->d_dists, c->d_ids, chain, c->knn, c->N,
                           cp, c->d_partials, c->stream, nbr ? (const P4<T>*)c->d_nbr : nullptr);
-    launch_finalize(c->d_partials, kRedBlocks, kCovNV, out, nullptr, c->stream);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = allreduce_f64(c, out, kCovNV))) return rc;  // (several ranks: the one extra collective per ICP)
+    if ((rc = finish_sums(c, cov))) return rc;  // (never inside a loop; several ranks: the one extra collective per ICP)
     double r[kCovNV];
-    HIPCHK(c, hipMemcpyAsync(r, out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r, cov.out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int a = 0;
     for (int i = 0; i < 6; ++i)
@@ -1694,8 +1676,8 @@ int get_weights_impl(pmx_ctx* c, void* w) {
     template int match_impl<T>(pmx_ctx*, const T*, int, double, uint64_t*);                  \
     template int outlier_impl<T>(pmx_ctx*, int, int, double, double, double);               \
     template int outlier_robust_impl<T>(pmx_ctx*, int, int, double, double, int, double, int); \
-    template int p2plane_enqueue<T>(pmx_ctx*);                                              \
-    template int p2point_enqueue<T>(pmx_ctx*, bool);                                        \
+    template int p2plane_enqueue<T>(pmx_ctx*, PendingSums*);                                \
+    template int p2point_enqueue<T>(pmx_ctx*, bool, PendingSums*);                          \
     template int p2plane_cov_impl<T>(pmx_ctx*, const T*, double*, double*, int64_t*);       \
     template int get_matches_impl<T>(pmx_ctx*, void*, int32_t*);                            \
     template int unpermute<T>(pmx_ctx*, const std::vector<T>&, T*, int);

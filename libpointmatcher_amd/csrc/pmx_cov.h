@@ -22,12 +22,7 @@
 
 namespace pmx {
 
-// values of the reduction: the upper triangle of H (21, row-major r <= c), the
-// kept-pair count, the upper triangle of Q (21)
-constexpr int kCovTri = 21;
-constexpr int kCovCount = kCovTri;
-constexpr int kCovQ = kCovTri + 1;
-constexpr int kCovNV = 2 * kCovTri + 1;
+// (values of the reduction: kCovCount, kCovQ, kCovNV of pmx_sums.h)
 
 // alpha, beta, gamma, t_x, t_y, t_z of the solved increment, in T
 // (PointToPlaneWithCov.cpp:94-99)
@@ -39,7 +34,7 @@ struct CovParams {
 // one kept pair: p the step reading point, q the centred reference point, n
 // its normal.  Every product and sum rounded to T separately, left to right as
 // the reference's expressions (:116-146); the products of the upper triangles
-// widened to double and added in fp64.  H: acc[0, 21), Q: acc[QO, QO + 21).
+// widened to double and added in fp64.  H first, Q from QO, kCovTri values each.
 template <typename T, bool WITH_H, bool WITH_Q, int QO, int NV>
 __device__ __forceinline__ void cov_add(double (&acc)[NV], T px, T py, T pz, const P4<T>& q, const P4<T>& n,
                                         const CovParams<T>& c) {

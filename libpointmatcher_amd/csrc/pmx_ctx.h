@@ -34,7 +34,8 @@
 using namespace pmx;
 
 // iteration block layout (see pmx_ctx_create)
-constexpr size_t kBlkSel = 1024;
+constexpr size_t kBlkSel = kResultDoubles * sizeof(double);  // (the result area first: pmx_sums.h)
+static_assert(kBlkSel == 1024, "iteration block layout");
 constexpr size_t kBlkIterErr = kBlkSel + sizeof(SelectState);
 constexpr size_t kBlkRatio = 1152;
 constexpr size_t kBlkVisited = 1216;
@@ -255,7 +256,7 @@ struct pmx_ctx {
 
     // reductions
     double* d_partials = nullptr;
-    double* d_result = nullptr;  // [0..63] system, [64..127] second pass
+    double* d_result = nullptr;  // kResultDoubles, then the select state (layout: pmx_sums.h)
     void* d_means = nullptr;
     double* h_result = nullptr;  // pinned
 
@@ -296,11 +297,6 @@ struct pmx_ctx {
     void* d_trace = nullptr;      // T_iter per iteration (keep_trace)
     long long* d_diag = nullptr;  // per-iteration diagnostics ring (kDiagCap x kDiagWords, pmx_loop_diag)
     unsigned int* d_ticket = nullptr;  // finalize_step_kernel's arrival ticket (0 between launches)
-    // device loop, one rank: the minimiser's last finalize is left to the
-    // fused finalize + step launch (final_out / final_nv: its accumulators)
-    bool fuse_final = false;
-    double* final_out = nullptr;
-    int final_nv = 0;
     int64_t trace_cap = 0;        // iterations
     bool loop_on = false;         // enqueueing loop iterations
     // quantile window fused into the grid match (pmx_spec.h): device loop,
@@ -400,8 +396,7 @@ int host_order(pmx_ctx* c);
 int select_reset(pmx_ctx* c);
 int ensure_level(pmx_ctx* c, int l);     // grid level l built (pmx_chain.hip)
 double host_limit(const pmx_ctx* c);
-void fill_stats(const pmx_ctx* c, pmx_stats* st, double kept, double nz, double rm, double rp, double sw,
-                double limit);
+void fill_stats(const pmx_ctx* c, pmx_stats* st, const SumStats& s, double limit);
 void side_join(pmx_ctx* c);
 void side_finish(pmx_ctx* c);
 template <typename T>
@@ -416,11 +411,18 @@ int outlier_impl(pmx_ctx* c, int kind, int chain_pos, double p0, double p1, doub
 template <typename T>
 int outlier_robust_impl(pmx_ctx* c, int pos, int fct, double tuning, double approx, int mode, double target,
                         int p2pl);
+// The minimisers' reductions enqueued, all but the last one's sum: *last names the partials
+// still to be finalized into out[0, nv), by finish_sums or the loop's fused finalize + step.
+struct PendingSums {
+    double* out;
+    int nv;
+};
+int finish_sums(pmx_ctx* c, const PendingSums& p);  // launch_finalize, then the ranks' sum
 template <typename T>
-int p2plane_enqueue(pmx_ctx* c);
+int p2plane_enqueue(pmx_ctx* c, PendingSums* last);
 // similarity: PointToPointSimilarity's sums (sigma after the moments, two passes always)
 template <typename T>
-int p2point_enqueue(pmx_ctx* c, bool similarity = false);
+int p2point_enqueue(pmx_ctx* c, bool similarity, PendingSums* last);
 template <typename T>
 int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* pairs);
 template <typename T>

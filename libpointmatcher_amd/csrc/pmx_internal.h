@@ -23,6 +23,8 @@
 #include <string>
 #include <vector>
 
+#include "pmx_sums.h"
+
 namespace pmx {
 
 template <typename T>
@@ -503,12 +505,7 @@ int vartrim_hdr_copy();     // int offset of the last call's counters in that sc
 
 // ---- reductions (pmx_reduce.hip) ----
 constexpr int kRedBlocks = 512;  // fixed reduction grid (deterministic sums; 256 / 1024 measured slower)
-constexpr int kNVMax = 48;
-// point-to-plane result layout: upper triangle of A (NS), b (NF), then kept,
-// nonzero weights, rejected matches, rejected points, sum of the weights
-constexpr int p2plane_nv(int dim) { return dim == 3 ? 21 + 6 + 5 : 6 + 3 + 5; }
-// the weighted (robust) variant: full A (NF x NF) instead of the upper triangle
-constexpr int p2plane_nv_full(int dim) { return dim == 3 ? 36 + 6 + 5 : 9 + 3 + 5; }
+// (the layout of every reduction's values: pmx_sums.h)
 // ctl / gd (device loop, may be null): early exit, step transform and the
 // grid level whose positions the ids are (ref / nrm then come from gd)
 // rs: index stride of ref / nrm (1: separate arrays; 2: a grid level's
@@ -528,7 +525,7 @@ void launch_p2point_pass1(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, 
 template <typename T>
 void launch_p2point_means(const double* sums, T* means_dev, int dim, const LoopCtl* ctl, hipStream_t s);
 // both passes' sums in one (device loop; the step centres the moments,
-// pmx_step.h): 20 values, layout in pmx_reduce.hip
+// pmx_step.h): P2PointSums::kMomentsNV values
 template <typename T>
 void launch_p2point_moments(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
                             const WChain<T>& chain, int k, int64_t N, double* partials, const LoopCtl* ctl,

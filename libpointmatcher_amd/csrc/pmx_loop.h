@@ -15,10 +15,6 @@ constexpr int kMaxLevels = 8;
 // window), pairs evaluated, full searches]
 constexpr int kDiagCap = 1024;
 constexpr int kDiagWords = 4;
-// doubles of the iteration block the step reads (point-to-plane: <= 36 + 6 +
-// 5 in the full layout; point-to-point: the second pass at 16..24, the
-// similarity minimiser's sigma at 25)
-constexpr int kStepRes = 48;
 
 enum CheckKind { kCheckCounter = 0, kCheckDifferential = 1, kCheckBound = 2 };
 // why the loop stopped

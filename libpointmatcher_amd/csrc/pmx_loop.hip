@@ -30,6 +30,30 @@
 
 namespace pmx {
 
+// the iteration's record in the diagnostics ring (pmx_loop.h), before the step moves the level
+template <typename T>
+__device__ __forceinline__ void diag_record(long long* __restrict__ diag, const LoopCtl* __restrict__ ctl,
+                                            const LoopState<T>* __restrict__ S, int hit, unsigned long long vis0,
+                                            unsigned long long vis1) {
+    if (!diag) return;
+    long long* rec = diag + (size_t)(S->iter % kDiagCap) * kDiagWords;
+    rec[0] = ctl->level;
+    rec[1] = hit;
+    rec[2] = (long long)vis0;
+    rec[3] = (long long)vis1;
+}
+
+// One instantiation of the step kernels per (rows, minimizer): LAUNCH(R, M) for cfg's pair.
+#define PMX_STEP_MIN(LAUNCH, R)  \
+    if (cfg.minimizer == 0)      \
+        LAUNCH(R, 0);            \
+    else if (cfg.minimizer == 1) \
+        LAUNCH(R, 1);            \
+    else                         \
+        LAUNCH(R, 2)
+#define PMX_STEP_DISPATCH(LAUNCH) \
+    if (cfg.rows == 4) { PMX_STEP_MIN(LAUNCH, 4); } else { PMX_STEP_MIN(LAUNCH, 3); }
+
 // The step after the minimiser (pmx_step.h); res holds the system (one lane
 // runs it; folding the last finalize into this launch measured slower: the
 // 256-thread step launch costs more than the finalize kernel it saves,
@@ -46,13 +70,7 @@ __global__ __launch_bounds__(64) void loop_step_kernel(LoopCtl* __restrict__ ctl
     const int e = *iter_err;
     const unsigned long long vis0 = visited[0], vis1 = visited[1];
     const int hit = spec_hit ? *spec_hit : -1;
-    if (diag) {
-        long long* r = diag + (size_t)(S->iter % kDiagCap) * kDiagWords;
-        r[0] = ctl->level;
-        r[1] = hit;
-        r[2] = (long long)vis0;
-        r[3] = (long long)vis1;
-    }
+    diag_record(diag, ctl, S, hit, vis0, vis1);
     step_body<T, ROWS, MIN>(ctl, S, res, e, vis0, vis1, means, cfg, trace);
 }
 
@@ -135,13 +153,7 @@ __global__ __launch_bounds__(256) void finalize_step_kernel(const double* __rest
         vis1 = visited[1];
     }
     const int hit = spec_hit ? *spec_hit : -1;
-    if (diag) {
-        long long* r = diag + (size_t)(S->iter % kDiagCap) * kDiagWords;
-        r[0] = ctl->level;
-        r[1] = hit;
-        r[2] = (long long)vis0;
-        r[3] = (long long)vis1;
-    }
+    diag_record(diag, ctl, S, hit, vis0, vis1);
     step_body<T, ROWS, MIN>(ctl, S, sres, e, vis0, vis1, means, cfg, trace);
 }
 
@@ -153,21 +165,7 @@ void launch_finalize_step(const double* partials, int nblocks, int nv, double* o
 #define PMX_FSTEP(R, M)                                                                                          \
     hipLaunchKernelGGL((finalize_step_kernel<T, R, M>), dim3(nv), dim3(256), 0, s, partials, nblocks, nv, out, res, \
                        ticket, ctl, S, iter_err, visited, means, cfg, trace, spec_hit, diag, vpart)
-    if (cfg.rows == 4) {
-        if (cfg.minimizer == 0)
-            PMX_FSTEP(4, 0);
-        else if (cfg.minimizer == 1)
-            PMX_FSTEP(4, 1);
-        else
-            PMX_FSTEP(4, 2);
-    } else {
-        if (cfg.minimizer == 0)
-            PMX_FSTEP(3, 0);
-        else if (cfg.minimizer == 1)
-            PMX_FSTEP(3, 1);
-        else
-            PMX_FSTEP(3, 2);
-    }
+    PMX_STEP_DISPATCH(PMX_FSTEP)
 #undef PMX_FSTEP
 }
 template void launch_finalize_step<float>(const double*, int, int, double*, double*, unsigned int*, LoopCtl*,
@@ -232,21 +230,7 @@ void launch_loop_step(LoopCtl* ctl, LoopState<T>* S, const double* res, const in
 #define PMX_STEP(R, M)                                                                                            \
     hipLaunchKernelGGL((loop_step_kernel<T, R, M>), dim3(1), dim3(64), 0, s, ctl, S, res, iter_err, visited, means, \
                        cfg, trace, spec_hit, diag)
-    if (cfg.rows == 4) {
-        if (cfg.minimizer == 0)
-            PMX_STEP(4, 0);
-        else if (cfg.minimizer == 1)
-            PMX_STEP(4, 1);
-        else
-            PMX_STEP(4, 2);
-    } else {
-        if (cfg.minimizer == 0)
-            PMX_STEP(3, 0);
-        else if (cfg.minimizer == 1)
-            PMX_STEP(3, 1);
-        else
-            PMX_STEP(3, 2);
-    }
+    PMX_STEP_DISPATCH(PMX_STEP)
 #undef PMX_STEP
 }
 template void launch_loop_init<float>(LoopCtl*, LoopState<float>*, const LoopCfg&, const float*, int, int,

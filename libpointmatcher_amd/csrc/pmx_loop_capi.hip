@@ -281,20 +281,19 @@ int loop_enqueue_iteration(pmx_ctx* c) {
         }
         if ((rc = outlier_impl<T>(c, cfg.filter_kind[i], i, p[0], p[1], p[2]))) return rc;
     }
-    // one rank: the minimiser's last finalize and the step in one launch
-    c->fuse_final = fuse_env && !sharded(c);
-    c->final_out = nullptr;
-    rc = cfg.minimizer == 0 ? p2plane_enqueue<T>(c) : p2point_enqueue<T>(c, c->loop_dev.minimizer == 2);
-    const bool fused = c->fuse_final && c->final_out;
-    c->fuse_final = false;
+    PendingSums last;
+    rc = cfg.minimizer == 0 ? p2plane_enqueue<T>(c, &last) : p2point_enqueue<T>(c, c->loop_dev.minimizer == 2, &last);
     const bool step_counter = c->step_counter;
     c->step_counter = false;
     if (rc) return rc;
+    // one rank: the minimiser's last finalize and the step in one launch
+    const bool fused = fuse_env && !sharded(c);
     if (step_counter && !fused) return fail(c, PMX_E_STATE, "device loop: counter phase left unfolded");
+    if (!fused && (rc = finish_sums(c, last))) return rc;
     const int* hitp = c->spec_on && c->d_spec ? &c->d_spec->hit : nullptr;
     T* trace = cfg.keep_trace ? (T*)c->d_trace : nullptr;
     if (fused)
-        launch_finalize_step<T>(c->d_partials, kRedBlocks, c->final_nv, c->final_out, c->d_result, c->d_ticket,
+        launch_finalize_step<T>(c->d_partials, kRedBlocks, last.nv, last.out, c->d_result, c->d_ticket,
                                 c->d_ctl, (LoopState<T>*)c->d_loop, c->d_iter_err, c->d_visited, (const T*)c->d_means,
                                 c->loop_dev, trace, hitp, c->d_diag, step_counter ? c->d_vpart : nullptr, c->stream);
     else
@@ -472,7 +471,7 @@ int loop_run_impl(pmx_ctx* c, int n, pmx_loop_status* st) {
         st->reason = S.reason;
         st->error = err;
         st->point_count_touched = (int64_t)S.touched;
-        fill_stats(c, &st->last, S.kept, S.nz, S.rejM, S.rejP, S.sw, host_limit(c));
+        fill_stats(c, &st->last, {S.kept, S.nz, S.rejM, S.rejP, S.sw}, host_limit(c));
         st->last.visited = (int64_t)S.last_visited;
         const int rr = c->rows * c->rows;
         for (int i = 0; i < rr; ++i) st->T_iter[i] = (double)S.Titer[i];

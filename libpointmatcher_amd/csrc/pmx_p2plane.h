@@ -98,14 +98,28 @@ __device__ __forceinline__ void block_store(double (&acc)[NV], double* __restric
     }
 }
 
+// One match entry in the ErrorElements counts from acc[S] (ErrorMinimizer.cpp:
+// 75-131); true for a kept pair.  A query with none is a rejected point (the
+// caller's count).  (p2plane_body keeps the rule written out: through this helper
+// its 2-D float form took 106 VGPRs instead of 92, 4 waves per SIMD instead of 5.)
+template <int S, int NV>
+__device__ __forceinline__ bool count_entry(double (&acc)[NV], bool nonzero, bool finite) {
+    if (nonzero) acc[S + kNonzero] += 1.0;  // (w != 0).count()
+    if (!finite) return false;
+    if (!nonzero) {
+        acc[S + kRejMatches] += 1.0;
+        return false;
+    }
+    acc[S + kKept] += 1.0;
+    return true;
+}
 
 // one kept pair: F and dot in T exactly as PointToPlane.cpp:171-243, the
 // upper triangle of F F^T and F dot added in fp64
 template <typename T, int DIM, int NV>
 __device__ __forceinline__ void p2plane_add(double (&acc)[NV], T px, T py, T pz, const P4<T>& q, const P4<T>& n,
                                             T w = (T)1) {
-    constexpr int NF = DIM == 3 ? 6 : 3;
-    constexpr int NS = NF * (NF + 1) / 2;
+    constexpr int NF = P2PlaneSums<DIM, false>::NF;
     T F[NF];
     T dot;
     if (DIM == 3) {
@@ -130,13 +144,12 @@ __device__ __forceinline__ void p2plane_add(double (&acc)[NV], T px, T py, T pz,
         const T wF = w * F[r];
 #pragma unroll
         for (int c = r; c < NF; ++c) acc[a++] += (double)(wF * F[c]);
-        acc[NS + r] += (double)(wF * dot);
+        acc[P2PlaneSums<DIM, false>::kB + r] += (double)(wF * dot);
     }
 }
 
-// result layout: [0, NS) upper triangle of A row-major (r <= c), [NS, NS+NF) b,
-// then kept, nonzero weights, rejected matches, rejected points, sum of weights;
-// one block's sums to partials[v * gridDim.x + blockIdx.x]
+// values: P2PlaneSums<DIM, false> (pmx_sums.h); one block's sums to
+// partials[v * gridDim.x + blockIdx.x]
 // k up to this: the reduction issues a query's k gathers together
 constexpr int kGatherK = 4;
 // SN: the chain holds the SurfaceNormalOutlierFilter (chain.sn, pmx_snormal.h):
@@ -149,9 +162,8 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
                                              const T* __restrict__ d, const int32_t* __restrict__ ids,
                                              const WChain<T>& chain, int k, int64_t N,
                                              double* __restrict__ partials, const P4<T>* __restrict__ nbr = nullptr) {
-    constexpr int NF = DIM == 3 ? 6 : 3;
-    constexpr int NS = NF * (NF + 1) / 2;
-    constexpr int NV = NS + NF + 5;  // (the fifth counter, sum of w, is the kept count with 0/1 weights)
+    constexpr int ST = P2PlaneSums<DIM, false>::kStats;  // (kSumW is the kept count with 0/1 weights)
+    constexpr int NV = P2PlaneSums<DIM, false>::NV;
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -209,14 +221,14 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
                     keep = keep && id[u] >= 0 && sn_pass(chain.sn, Tm, rn[u], n[u]);
                     kp[u] = kp[u] && keep;
                 }
-                if (keep) acc[NS + NF + 1] += 1.0;                 // (w != 0).count()
-                if (dv[u] != inf && !keep) acc[NS + NF + 2] += 1.0;  // rejected match
+                if (keep) acc[ST + kNonzero] += 1.0;
+                if (dv[u] != inf && !keep) acc[ST + kRejMatches] += 1.0;
                 if (!kp[u]) {
-                    acc[NS + NF + 3] += 1.0;  // rejected point
+                    acc[ST + kRejPoints] += 1.0;
                     continue;
                 }
-                acc[NS + NF + 0] += 1.0;
-                acc[NS + NF + 4] += 1.0;
+                acc[ST + kKept] += 1.0;
+                acc[ST + kSumW] += 1.0;
                 T px, py, pz;
                 xform3(Tm, r[u], px, py, pz);
                 p2plane_add<T, DIM, NV>(acc, px, py, pz, q[u], n[u]);
@@ -257,18 +269,18 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
                 if (s >= k) continue;
                 bool keep = chain_keep(wr, dv[s]);
                 if (SN) keep = keep && id[s] >= 0 && sn_pass(chain.sn, Tm, rn, n[s]);
-                if (keep) acc[NS + NF + 1] += 1.0;  // (w != 0).count()
+                if (keep) acc[ST + kNonzero] += 1.0;
                 if (dv[s] == inf) continue;
                 if (!keep) {
-                    acc[NS + NF + 2] += 1.0;  // rejected match
+                    acc[ST + kRejMatches] += 1.0;
                     continue;
                 }
                 exist = true;
-                acc[NS + NF + 0] += 1.0;  // kept
-                acc[NS + NF + 4] += 1.0;  // sum of the 0/1 weights
+                acc[ST + kKept] += 1.0;
+                acc[ST + kSumW] += 1.0;  // (the 0/1 weights)
                 p2plane_add<T, DIM, NV>(acc, px, py, pz, q[s], n[s]);
             }
-            if (!exist) acc[NS + NF + 3] += 1.0;  // rejected point
+            if (!exist) acc[ST + kRejPoints] += 1.0;
         }
     }
     for (int64_t i = i0; k != 1 && i < N; i += stride) {
@@ -283,19 +295,19 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
                 const int32_t id = ids[e];
                 keep = keep && id >= 0 && sn_pass(chain.sn, Tm, gld(chain.sn.rn, i), gld(nrm, (int64_t)id * rs));
             }
-            if (keep) acc[NS + NF + 1] += 1.0;  // (w != 0).count()
+            if (keep) acc[ST + kNonzero] += 1.0;
             if (dv == inf) continue;
             if (!keep) {
-                acc[NS + NF + 2] += 1.0;  // rejected match
+                acc[ST + kRejMatches] += 1.0;
                 continue;
             }
             exist = true;
-            acc[NS + NF + 0] += 1.0;  // kept
-            acc[NS + NF + 4] += 1.0;  // sum of the 0/1 weights
+            acc[ST + kKept] += 1.0;
+            acc[ST + kSumW] += 1.0;  // (the 0/1 weights)
             const int32_t id = ids[e];
             p2plane_add<T, DIM, NV>(acc, px, py, pz, gld(ref, (int64_t)id * rs), gld(nrm, (int64_t)id * rs));
         }
-        if (!exist) acc[NS + NF + 3] += 1.0;  // rejected point
+        if (!exist) acc[ST + kRejPoints] += 1.0;
     }
     block_store<NV, kCoherent>(acc, partials);
 }

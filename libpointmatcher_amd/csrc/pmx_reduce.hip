@@ -52,8 +52,7 @@ __device__ __forceinline__ T pair_weight(const WChain<T>& chain, const SNPred<T>
     return w;
 }
 
-// result layout: [0, NS) upper triangle of A row-major (r <= c), [NS, NS+NF) b,
-// then kept, nonzero weights, rejected matches, rejected points
+// (values: P2PlaneSums<DIM, false>, pmx_sums.h)
 template <typename T, int DIM, bool SN>
 __global__ __launch_bounds__(256) void p2plane_partial_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                               const P4<T>* __restrict__ ref,
@@ -81,10 +80,12 @@ __global__ __launch_bounds__(256) void p2plane_partial_kernel(const P4<T>* __res
 // the ErrorElements counts on w != 0, sum of w in the fifth counter.  A is
 // accumulated in full: (w F_r) F_c and (w F_c) F_r round differently, and the
 // reference's wF * F^T keeps that asymmetry (PointToPlane.cpp:218-227).
+// (values: P2PlaneSums<DIM, true>, pmx_sums.h)
 template <typename T, int DIM, int NV>
 __device__ __forceinline__ void p2plane_add_full(double (&acc)[NV], T px, T py, T pz, const P4<T>& q,
                                                  const P4<T>& n, T w) {
-    constexpr int NF = DIM == 3 ? 6 : 3;
+    using L = P2PlaneSums<DIM, true>;
+    constexpr int NF = L::NF;
     T F[NF];
     T dot;
     if (DIM == 3) {
@@ -106,7 +107,7 @@ __device__ __forceinline__ void p2plane_add_full(double (&acc)[NV], T px, T py, 
         const T wF = w * F[r];
 #pragma unroll
         for (int c = 0; c < NF; ++c) acc[r * NF + c] += (double)(wF * F[c]);
-        acc[NF * NF + r] += (double)(wF * dot);
+        acc[L::kB + r] += (double)(wF * dot);
     }
 }
 template <typename T, int DIM, bool SN>
@@ -125,9 +126,8 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
         nrm = ref + 1;
         rs = 2;
     }
-    constexpr int NF = DIM == 3 ? 6 : 3;
-    constexpr int NS = NF * NF;  // (full A)
-    constexpr int NV = NS + NF + 5;
+    using L = P2PlaneSums<DIM, true>;
+    constexpr int NV = L::NV;
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -153,18 +153,12 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
             const T sc = (T)*chain.rb_scale;
             T w = pred * robust_weight<T>(chain.rb_fct, chain.rb_k, chain.rb_sqa, dist / (sc * sc));
             if (SN) w = w * (id >= 0 && sn_pass(chain.sn, Tm, gld(chain.sn.rn, i), n) ? (T)1 : (T)0);
-            if (w != (T)0) acc[NS + NF + 1] += 1.0;  // (w != 0).count()
-            if (dv == inf) continue;
-            if (w == (T)0) {
-                acc[NS + NF + 2] += 1.0;  // rejected match
-                continue;
-            }
+            if (!count_entry<L::kStats>(acc, w != (T)0, dv != inf)) continue;
             exist = true;
-            acc[NS + NF + 0] += 1.0;
-            acc[NS + NF + 4] += (double)w;
+            acc[L::kStats + kSumW] += (double)w;
             p2plane_add_full<T, DIM, NV>(acc, px, py, pz, q, n, w);
         }
-        if (!exist) acc[NS + NF + 3] += 1.0;
+        if (!exist) acc[L::kStats + kRejPoints] += 1.0;
     }
     block_store<NV>(acc, partials);
 }
@@ -209,8 +203,66 @@ void launch_finalize(const double* partials, int nblocks, int nv, double* out, c
 }
 
 // ------------------------------------------------------------ point-to-point --
-// pass 1: sum w, sum p*w, sum q*w (PointToPoint.cpp:67-72) + ErrorElements counts
-// layout: [0] sw, [1..3] sp, [4..6] sq, [7] kept, [8] nz, [9] rejM, [10] rejP
+// (values: P2PointSums, pmx_sums.h)
+// What the three kernels do first: in the device loop (ctl) the step transform,
+// the level's points and normals from the device.  sn: the caller's copy of chain.sn
+// (writing the kernel argument would move the chain to scratch).  False: the loop is done.
+template <typename T, bool SN>
+__device__ __forceinline__ bool p2point_begin(const LoopCtl* __restrict__ ctl, const GridDesc<T>* __restrict__ gd,
+                                              Mat4<T>& Tm, const P4<T>* __restrict__& ref, SNPred<T>& sn) {
+    if (ctl) {
+        if (ctl->done) return false;
+        ctl_transform(ctl, Tm);
+        ref = gd[ctl->level].gpts;
+    }
+    if (SN) sn_bind(sn, ctl, gd);
+    return true;
+}
+
+// pass 1: sum w, sum p*w, sum q*w (PointToPoint.cpp:67-72; with w = 1,
+// p * w == p exactly) + ErrorElements counts; RAW: the one-pass form's raw
+// moments sum (w q_r) p_c as well.  block: this block's place in the walk.
+template <typename T, bool SN, bool RAW>
+__device__ __forceinline__ void p2point_sums_body(const P4<T>* __restrict__ rd, const Mat4<T>& Tm,
+                                                  const P4<T>* __restrict__ ref, const T* __restrict__ d,
+                                                  const int32_t* __restrict__ ids, const WChain<T>& chain,
+                                                  const SNPred<T>& sn, int k, int64_t N, uint32_t block,
+                                                  double* __restrict__ partials) {
+    using L = P2PointSums;
+    constexpr int NV = RAW ? L::kMomentsNV : L::kPass1NV;
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    const WRange<T> wr = chain_resolve(chain);
+    const T inf = (T)__builtin_huge_val();
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)block * blockDim.x + threadIdx.x; i < N; i += stride) {
+        T p[3];
+        xform3(Tm, rd[i], p[0], p[1], p[2]);
+        bool exist = false;
+        for (int s = 0; s < k; ++s) {
+            const int64_t e = i * k + s;
+            const T dv = d[e];
+            // 0/1 weights, or a robust chain's real weight (point2point distance)
+            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
+            if (!count_entry<L::kStats>(acc, w != (T)0, dv != inf)) continue;
+            exist = true;
+            const P4<T> q = gld(ref, ids[e]);
+            const T wq[3] = {q.x * w, q.y * w, q.z * w};
+            acc[L::kSw] += (double)w;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                acc[L::kSp + r] += (double)(p[r] * w);
+                acc[L::kSq + r] += (double)wq[r];
+#pragma unroll
+                for (int c = 0; RAW && c < 3; ++c) acc[L::kRaw + L::moment(r, c)] += (double)wq[r] * (double)p[c];
+            }
+        }
+        if (!exist) acc[L::kStats + kRejPoints] += 1.0;
+    }
+    block_store<NV>(acc, partials);
+}
+
 template <typename T, bool SN>
 __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                             const P4<T>* __restrict__ ref, const T* __restrict__ d,
@@ -218,50 +270,9 @@ __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restr
                                                             int64_t N, double* __restrict__ partials,
                                                             const LoopCtl* __restrict__ ctl,
                                                             const GridDesc<T>* __restrict__ gd) {
-    constexpr int NV = 11;
-    if (ctl) {  // device loop
-        if (ctl->done) return;
-        ctl_transform(ctl, Tm);
-        ref = gd[ctl->level].gpts;
-    }
-    SNPred<T> sn = chain.sn;  // (a copy: writing the kernel argument would move the chain to scratch)
-    if (SN) sn_bind(sn, ctl, gd);
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    const WRange<T> wr = chain_resolve(chain);
-    const T inf = (T)__builtin_huge_val();
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride) {
-        T px, py, pz;
-        xform3(Tm, rd[i], px, py, pz);
-        bool exist = false;
-        for (int s = 0; s < k; ++s) {
-            const int64_t e = i * k + s;
-            const T dv = d[e];
-            // 0/1 weights, or a robust chain's real weight (point2point distance)
-            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
-            if (w != (T)0) acc[8] += 1.0;
-            if (dv == inf) continue;
-            if (w == (T)0) {
-                acc[9] += 1.0;
-                continue;
-            }
-            exist = true;
-            acc[7] += 1.0;
-            const P4<T> q = gld(ref, ids[e]);
-            // (with w = 1, p * w == p exactly)
-            acc[0] += (double)w;
-            acc[1] += (double)(px * w);
-            acc[2] += (double)(py * w);
-            acc[3] += (double)(pz * w);
-            acc[4] += (double)(q.x * w);
-            acc[5] += (double)(q.y * w);
-            acc[6] += (double)(q.z * w);
-        }
-        if (!exist) acc[10] += 1.0;
-    }
-    block_store<NV>(acc, partials);
+    SNPred<T> sn = chain.sn;
+    if (!p2point_begin<T, SN>(ctl, gd, Tm, ref, sn)) return;
+    p2point_sums_body<T, SN, false>(rd, Tm, ref, d, ids, chain, sn, k, N, blockIdx.x, partials);
 }
 
 template <typename T>
@@ -277,10 +288,10 @@ template <typename T>
 __global__ void p2point_means_kernel(const double* __restrict__ sums, T* __restrict__ means, int dim,
                                      const LoopCtl* __restrict__ ctl) {
     if (threadIdx.x != 0 || (ctl && ctl->done)) return;
-    const T winv = (T)1 / (T)sums[0];
+    const T winv = (T)1 / (T)sums[P2PointSums::kSw];
     for (int r = 0; r < 3; ++r) {
-        means[r] = r < dim ? (T)sums[1 + r] * winv : (T)0;
-        means[3 + r] = r < dim ? (T)sums[4 + r] * winv : (T)0;
+        means[r] = r < dim ? (T)sums[P2PointSums::kSp + r] * winv : (T)0;
+        means[3 + r] = r < dim ? (T)sums[P2PointSums::kSq + r] * winv : (T)0;
     }
 }
 
@@ -302,14 +313,10 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
                                                             double* __restrict__ partials,
                                                             const LoopCtl* __restrict__ ctl,
                                                             const GridDesc<T>* __restrict__ gd) {
-    constexpr int NV = SIM ? 10 : 9;
-    if (ctl) {  // device loop
-        if (ctl->done) return;
-        ctl_transform(ctl, Tm);
-        ref = gd[ctl->level].gpts;
-    }
-    SNPred<T> sn = chain.sn;  // (a copy: writing the kernel argument would move the chain to scratch)
-    if (SN) sn_bind(sn, ctl, gd);
+    using L = P2PointSums;
+    constexpr int NV = SIM ? L::kPass2SimNV : L::kPass2NV;
+    SNPred<T> sn = chain.sn;
+    if (!p2point_begin<T, SN>(ctl, gd, Tm, ref, sn)) return;
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -337,9 +344,10 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) acc[r * 3 + c] += (double)((qc[r] * w) * pc[c]);  // (qc * w) pc
+                for (int c = 0; c < 3; ++c) acc[L::moment(r, c)] += (double)((qc[r] * w) * pc[c]);  // (qc * w) pc
             }
-            if constexpr (SIM) acc[9] += (double)(((pc[0] * pc[0] + pc[1] * pc[1]) + pc[2] * pc[2]) * w);
+            if constexpr (SIM)  // (sigma behind the moments: kSigma of the result area)
+                acc[L::kPass2NV] += (double)(((pc[0] * pc[0] + pc[1] * pc[1]) + pc[2] * pc[2]) * w);
         }
     }
     block_store<NV>(acc, partials);
@@ -362,8 +370,6 @@ void launch_p2point_pass2(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, 
 // fp64: sum w (q - mq)(p - mp)^T = sum (w q) p^T - mq (sum w p)^T
 // - (sum w q) mp^T + (sum w) mq mp^T (PointToPoint.cpp:67-81 by the same
 // identity; the two-pass kernels above are the per-module path's).
-// Layout: [0] sum w, [1, 4) sum w p, [4, 7) sum w q, [7, 11) kept, nonzero
-// weights, rejected matches, rejected points, [11, 20) sum (w q_r) p_c.
 template <typename T, bool SN>
 __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                               const P4<T>* __restrict__ ref, const T* __restrict__ d,
@@ -371,53 +377,9 @@ __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __res
                                                               int64_t N, double* __restrict__ partials,
                                                               const LoopCtl* __restrict__ ctl,
                                                               const GridDesc<T>* __restrict__ gd) {
-    constexpr int NV = 20;
-    if (ctl) {  // device loop
-        if (ctl->done) return;
-        ctl_transform(ctl, Tm);
-        ref = gd[ctl->level].gpts;
-    }
-    SNPred<T> sn = chain.sn;  // (a copy: writing the kernel argument would move the chain to scratch)
-    if (SN) sn_bind(sn, ctl, gd);
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    const WRange<T> wr = chain_resolve(chain);
-    const T inf = (T)__builtin_huge_val();
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)xcd_block() * blockDim.x + threadIdx.x; i < N; i += stride) {
-        T px, py, pz;
-        xform3(Tm, rd[i], px, py, pz);
-        bool exist = false;
-        for (int s = 0; s < k; ++s) {
-            const int64_t e = i * k + s;
-            const T dv = d[e];
-            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
-            if (w != (T)0) acc[8] += 1.0;
-            if (dv == inf) continue;
-            if (w == (T)0) {
-                acc[9] += 1.0;
-                continue;
-            }
-            exist = true;
-            acc[7] += 1.0;
-            const P4<T> q = gld(ref, ids[e]);
-            const T wq[3] = {q.x * w, q.y * w, q.z * w};
-            const double p[3] = {(double)px, (double)py, (double)pz};
-            acc[0] += (double)w;
-            acc[1] += (double)(px * w);
-            acc[2] += (double)(py * w);
-            acc[3] += (double)(pz * w);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                acc[4 + r] += (double)wq[r];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc[11 + r * 3 + c] += (double)wq[r] * p[c];
-            }
-        }
-        if (!exist) acc[10] += 1.0;
-    }
-    block_store<NV>(acc, partials);
+    SNPred<T> sn = chain.sn;
+    if (!p2point_begin<T, SN>(ctl, gd, Tm, ref, sn)) return;
+    p2point_sums_body<T, SN, true>(rd, Tm, ref, d, ids, chain, sn, k, N, xcd_block(), partials);
 }
 
 template <typename T>

@@ -60,27 +60,16 @@ __device__ void quat_of(const T* M, int rows, bool init2d, T* q) {
     quat_from_matrix(m3, q);
 }
 
-// The normal equations of the point-to-plane step as T (PointToPlane.cpp:230, 243)
-template <typename T, int NF>
-__device__ __forceinline__ void p2plane_system_of(const double* __restrict__ res, T* A, T* b) {
-    constexpr int NS = NF * (NF + 1) / 2;
-    int a = 0;
-    for (int i = 0; i < NF; ++i)
-        for (int j = i; j < NF; ++j, ++a) A[i * NF + j] = A[j * NF + i] = (T)res[a];
-    for (int i = 0; i < NF; ++i) b[i] = (T)(-res[NS + i]);
-}
-
 // Rank-deficient point-to-plane system: rare, kept out of line so that its
 // dynamically indexed work arrays do not push the hot path's into scratch.
-template <typename T, int NF>
+template <typename T, int DIM>
 __device__ __noinline__ void loop_solve_rank_deficient(const double* __restrict__ res, int full, T* __restrict__ xout) {
+    constexpr int NF = P2PlaneSums<DIM, false>::NF;
     T A[36], b[6], x[6];
-    if (full) {
-        for (int i = 0; i < NF * NF; ++i) A[i] = (T)res[i];
-        for (int i = 0; i < NF; ++i) b[i] = (T)(-res[NF * NF + i]);
-    } else {
-        p2plane_system_of<T, NF>(res, A, b);
-    }
+    if (full)
+        p2plane_unpack<T, DIM, true>(res, A, b);
+    else
+        p2plane_unpack<T, DIM, false>(res, A, b);
     solve_rank_deficient(A, b, NF, x);
     for (int i = 0; i < NF; ++i) xout[i] = x[i];
 }
@@ -128,8 +117,8 @@ __device__ __forceinline__ bool well_conditioned(const T* A, const T* L) {
            (T)1 / s >= ratio * sqrt(fa);
 }
 
-// One lane: res = the minimiser's sums (point-to-plane layout, or
-// point-to-point's two passes at 0 and 16), e = the iteration's error word,
+// One lane: res = the minimiser's sums (the result area's first kStepRes
+// doubles, pmx_sums.h), e = the iteration's error word,
 // vis0 / vis1 = the match's pair evaluations and full searches.
 // ROWS is the homogeneous dimension (4 in 3-D, 3 in 2-D): with every size a
 // compile-time constant the dense kit's arrays live in VGPRs, not scratch
@@ -155,21 +144,7 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
 #pragma unroll
     for (int ci = 0; ci < kMaxCheckers; ++ci) cnt[ci] = S->cond[ci][0];
     // statistics of the iteration (ErrorElements, ErrorMinimizer.cpp:133-192)
-    double kept, nz, rejM, rejP, sw;
-    if (MIN == 0) {
-        const int NF = D == 3 ? 6 : 3, o = (cfg.full ? NF * NF : NF * (NF + 1) / 2) + NF;
-        kept = res[o];
-        nz = res[o + 1];
-        rejM = res[o + 2];
-        rejP = res[o + 3];
-        sw = res[o + 4];
-    } else {
-        kept = res[7];
-        nz = res[8];
-        rejM = res[9];
-        rejP = res[10];
-        sw = res[0];
-    }
+    const SumStats st = MIN == 0 ? p2plane_stats<D>(res, cfg.full != 0) : p2point_stats(res);
     S->last_level = level_now;  // the level whose positions this iteration's ids are
     // the next match may reuse this one's output (pmx_grid.hip temporal reuse)
     for (int i = 0; i < 16; ++i) ctl->Tprev[i] = ctl->T[i];
@@ -178,42 +153,29 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
         loop_fail(ctl, S, e, kLoopError);
         return;
     }
-    if (nz == 0.0 || kept == 0.0) {
+    if (st.nz == 0.0 || st.kept == 0.0) {
         loop_fail(ctl, S, kLoopNoPoints, kLoopError);  // "ErrorMnimizer: no point to minimize"
         return;
     }
     // the minimiser returned: its statistics and the matcher's visit counter
     // (ICP.cpp:406-416, MatchersImpl.cpp:98)
-    S->kept = kept;
-    S->nz = nz;
-    S->rejM = rejM;
-    S->rejP = rejP;
-    S->sw = sw;
+    S->kept = st.kept;
+    S->nz = st.nz;
+    S->rejM = st.rejM;
+    S->rejP = st.rejP;
+    S->sw = st.sw;
     S->last_visited = vis0;
     S->touched += vis0;
     // the step transform
     T dT[16];
-    if constexpr (MIN == 2) {
-        // PointToPointSimilarity: the two passes' means and moments, sigma
-        // behind them (p2point_enqueue); p2p_onepass is the rigid minimiser's
-        T m[9], mp[3], mq[3];
-        for (int i = 0; i < D; ++i) {
-            mp[i] = means[i];
-            mq[i] = means[3 + i];
-            for (int j = 0; j < D; ++j) m[i * D + j] = (T)res[16 + i * 3 + j];
-        }
-        p2point_similarity_transform(rows, m, mp, mq, (T)res[25], dT);
-    } else if constexpr (MIN == 0) {
-        constexpr int NF = D == 3 ? 6 : 3;
+    if constexpr (MIN == 0) {
+        constexpr int NF = P2PlaneSums<D, false>::NF;
         T A[NF * NF], b[NF], x[NF], L[NF * NF];
-        if (cfg.full) {  // (a robust chain: (w F_r) F_c in T, the reference's asymmetric wF * F^T)
-#pragma unroll
-            for (int i = 0; i < NF * NF; ++i) A[i] = (T)res[i];
-#pragma unroll
-            for (int i = 0; i < NF; ++i) b[i] = (T)(-res[NF * NF + i]);
-        } else {
-            p2plane_system_of<T, NF>(res, A, b);
-        }
+        // (full: a robust chain, (w F_r) F_c in T, the reference's asymmetric wF * F^T)
+        if (cfg.full)
+            p2plane_unpack<T, D, true>(res, A, b);
+        else
+            p2plane_unpack<T, D, false>(res, A, b);
         // solve_full_rank: FullPivQR(A).isInvertible() -> LLT solve.  The
         // QR's rank test is skipped when the LLT factor proves A far from
         // rank-deficient (well_conditioned below): its answer is then known.
@@ -227,33 +189,39 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
         if (full) {
             llt_solve(L, NF, b, x);
         } else {
-            loop_solve_rank_deficient<T, NF>(res, cfg.full, S->xsolve);
+            loop_solve_rank_deficient<T, D>(res, cfg.full, S->xsolve);
             for (int i = 0; i < NF; ++i) x[i] = S->xsolve[i];
         }
         p2plane_transform(rows, x, dT);
     } else {
+        using PS = P2PointSums;
         T m[9], mp[3], mq[3];
-        if (cfg.p2p_onepass) {
+        if (MIN == 1 && cfg.p2p_onepass) {  // (the rigid minimiser's; never the similarity's)
             // one moments pass (launch_p2point_moments): the weighted means in
             // T (p2point_means_kernel's arithmetic), the moments centred in fp64
-            const T winv = (T)1 / (T)res[0];
+            const double sw = res[PS::kSw];
+            const double *sp = res + PS::kSp, *sq = res + PS::kSq, *raw = res + PS::kRaw;
+            const T winv = (T)1 / (T)sw;
             for (int i = 0; i < D; ++i) {
-                mp[i] = (T)res[1 + i] * winv;
-                mq[i] = (T)res[4 + i] * winv;
+                mp[i] = (T)sp[i] * winv;
+                mq[i] = (T)sq[i] * winv;
             }
             for (int i = 0; i < D; ++i)
                 for (int j = 0; j < D; ++j) {
                     const double a = (double)mq[i], bb = (double)mp[j];
-                    m[i * D + j] = (T)(((res[11 + i * 3 + j] - a * res[1 + j]) - res[4 + i] * bb) + res[0] * a * bb);
+                    m[i * D + j] = (T)(((raw[PS::moment(i, j)] - a * sp[j]) - sq[i] * bb) + sw * a * bb);
                 }
-        } else {
+        } else {  // the two passes' means and centred moments (p2point_enqueue)
             for (int i = 0; i < D; ++i) {
                 mp[i] = means[i];
                 mq[i] = means[3 + i];
-                for (int j = 0; j < D; ++j) m[i * D + j] = (T)res[16 + i * 3 + j];
+                for (int j = 0; j < D; ++j) m[i * D + j] = (T)res[PS::kPass2At + PS::moment(i, j)];
             }
         }
-        p2point_transform(rows, m, mp, mq, dT);
+        if constexpr (MIN == 2)
+            p2point_similarity_transform(rows, m, mp, mq, (T)res[PS::kSigma], dT);
+        else
+            p2point_transform(rows, m, mp, mq, dT);
     }
     if (cfg.keep_increment) {  // (PointToPlaneWithCovErrorMinimizer: the covariance is estimated at it)
 #pragma unroll
