@@ -192,6 +192,108 @@ def planar_grid():
     return pts, pts1
 
 
+# ---- the quantile select's reference and its adversarial key sets ----
+TRIMMED, MEDIAN = "TrimmedDistOutlierFilter", "MedianDistOutlierFilter"
+
+
+def quantile_rank(count, kind, ratio, dtype):
+    """Matches.cpp:83-86 in T: int(T(count) * T(ratio)) clamped to count - 1,
+    ratio == 1 the maximum; Median: count // 2 (Matches.cpp:110-120)."""
+    T = np.dtype(dtype).type
+    if kind == MEDIAN:
+        return count // 2
+    q = T(ratio)
+    if q == T(1):
+        return count - 1
+    return min(int(T(count) * q), count - 1)
+
+
+def quantile_value(d, kind, ratio, dtype):
+    """The order statistic itself: the finite distances (not +inf,
+    Matches.cpp:71) sorted, read at quantile_rank.  Raises LookupError when
+    nothing is finite ("no outlier to filter")."""
+    d = np.asarray(d, dtype=dtype)
+    fin = np.sort(d[d != np.inf], axis=None)
+    if fin.size == 0:
+        raise LookupError("no outlier to filter")
+    return fin[quantile_rank(fin.size, kind, ratio, dtype)]
+
+
+def quantile_limit(d, kind, ratio, dtype):
+    """(limit, weights) of TrimmedDist (ratio) / MedianDist (ratio = its
+    factor; limit = factor * median in T, OutlierFiltersImpl.cpp:121-122) by a
+    plain sort; weights = d <= limit, in d's shape."""
+    T = np.dtype(dtype).type
+    v = quantile_value(d, kind, ratio, dtype)
+    limit = T(ratio) * v if kind == MEDIAN else v
+    return limit, (np.asarray(d, dtype=dtype) <= limit).astype(dtype)
+
+
+def select_filters(dtype):
+    """The filters every select case runs: Trimmed at a ratio that gives rank
+    0, two inner ratios, the largest T below 1, and 1 (the maximum); Median."""
+    T = np.dtype(dtype).type
+    below1 = float(np.nextafter(T(1), T(0)))
+    return [(TRIMMED, 1e-6), (TRIMMED, 0.3), (TRIMMED, 0.85), (TRIMMED, below1), (TRIMMED, 1.0), (MEDIAN, 3.0)]
+
+
+def filter_params(kind, p):
+    return {"factor": p} if kind == MEDIAN else {"ratio": p}
+
+
+SELECT_SIZES = (1, 2, 15, 16, 17, 4095, 4096, 4097, 8193, 40_000, 262_145)
+SELECT_KEY_SETS = ("lastdigit", "equal", "zero", "two_values", "decades")
+
+
+def select_reading_x(tag, n, dtype):
+    """x coordinates of n reading points whose squared distances to one
+    reference point at the origin, d_i = fl(x_i^2), form the key set `tag`."""
+    T = np.dtype(dtype).type
+    i = np.arange(n)
+    if tag == "lastdigit":  # keys that share every digit but the last one or two
+        return (T(1) + i.astype(dtype) * T(2.0 ** (-23 if T is np.float32 else -52))).astype(dtype)
+    if tag == "equal":
+        return np.full(n, 0.5, dtype)
+    if tag == "zero":
+        return np.zeros(n, dtype)
+    if tag == "two_values":  # 80 % at 2^-4, 20 % at 2^-2, interleaved
+        return np.where(i % 5 == 4, T(0.25), T(0.0625)).astype(dtype)
+    if tag == "decades":
+        return np.power(T(10), np.linspace(-18, 3, n, dtype=dtype)).astype(dtype)
+    raise KeyError(tag)
+
+
+def select_reading(x):
+    """The reading of select_reading_x's points: (n, 4), on the x axis."""
+    rd = np.zeros((len(x), 4), x.dtype)
+    rd[:, 0] = x
+    rd[:, 3] = 1
+    return rd
+
+
+def max_dist_keeping(x, m):
+    """A matcher maxDist between the m-th and the (m+1)-th smallest |x| (their
+    geometric mean): exactly m points stay within it."""
+    s = np.sort(np.abs(np.asarray(x, np.float64)))
+    return float(np.sqrt(s[m - 1] * s[m]))
+
+
+def matched_dists(x, max_dist=np.inf):
+    """What the matcher returns for select_reading(x) against the origin:
+    fl(x^2), +inf beyond maxDist (squared in T, as libnabo does); (n, 1)."""
+    T = x.dtype.type
+    d = (x * x).astype(x.dtype)
+    if np.isfinite(max_dist):
+        d = np.where(d <= T(max_dist) * T(max_dist), d, T(np.inf)).astype(x.dtype)
+    return d.reshape(-1, 1)
+
+
+def key_bits(d):
+    """IEEE bit patterns of non-negative distances (the select's keys)."""
+    d = np.ascontiguousarray(d)
+    return d.view(np.uint32 if d.dtype == np.float32 else np.uint64).ravel()
+
+
 CHAIN_P2PLANE = """
 readingDataPointsFilters:
   - IdentityDataPointsFilter:
