@@ -322,6 +322,13 @@ int build_one_level(pmx_ctx* c, int l, const SetupScratch& sc, hipStream_t st) {
     return PMX_OK;
 }
 
+// a grid level as the kernels see it
+template <typename T>
+GridDesc<T> level_desc(const GridLevel& L) {
+    return {(const P4<T>*)L.gpts, (const P4<T>*)L.gpn, L.gidx, L.gstart,
+            {{L.lo[0], L.lo[1], L.lo[2]}, L.h, 1.0 / L.h, {L.dim[0], L.dim[1], L.dim[2]}}};
+}
+
 // the device table of levels [0, levels_built) (the device loop picks the
 // level on the GPU, among the built ones)
 template <typename T>
@@ -334,20 +341,7 @@ int publish_levels(pmx_ctx* c) {
     }
     HIPCHK(c, hipEventSynchronize(c->table_ev));  // (the previous table's copy has read the staging)
     GridDesc<T>* tab = (GridDesc<T>*)c->h_table;
-    for (size_t l = 0; l < (size_t)c->levels_built; ++l) {
-        const GridLevel& L = c->levels[l];
-        GridDesc<T>& D = tab[l];
-        D.gpts = (const P4<T>*)L.gpts;
-        D.gpn = (const P4<T>*)L.gpn;
-        D.gidx = L.gidx;
-        D.start = L.gstart;
-        for (int a = 0; a < 3; ++a) {
-            D.G.lo[a] = L.lo[a];
-            D.G.g[a] = L.dim[a];
-        }
-        D.G.h = L.h;
-        D.G.inv_h = 1.0 / L.h;
-    }
+    for (size_t l = 0; l < (size_t)c->levels_built; ++l) tab[l] = level_desc<T>(c->levels[l]);
     if (!c->d_gdesc) HIPCHK(c, hipMalloc(&c->d_gdesc, sizeof(GridDesc<T>) * kMaxLevels));
     // (stream-ordered and asynchronous: the host goes on — the reading's
     // upload overlaps the level builds still running)
@@ -669,14 +663,12 @@ int set_reading_impl(pmx_ctx* c, const T* feat, int rows, int64_t N, const T* T0
 }
 
 // ------------------------------------------------------------------- match --
+// room for the match of N x knn pairs: distances, ids, weights, the safe
+// radii of the temporal reuse and the brute-force partial lists
 template <typename T>
-int match_impl(pmx_ctx* c, const T* Titer, int knn, double maxDist, uint64_t* visited) {
-    if (!c->d_ref) return fail(c, PMX_E_STATE, "no reference (Matcher::init not called)");
-    if (!c->d_rd && c->N > 0) return fail(c, PMX_E_STATE, "no reading");
-    if (knn < 1) return fail(c, PMX_E_BAD_PARAM, "knn must be >= 1");
-    if (!(maxDist >= 0)) return fail(c, PMX_E_BAD_PARAM, "maxDist must be >= 0");
+int match_room(pmx_ctx* c, int knn) {
     const int64_t n = c->N * knn;
-    size_t cap = (size_t)c->match_cap * tsize(c);
+    int rc;
     if ((int64_t)c->match_cap < n || !c->d_dists) {
         size_t capd = 0, capi = 0, capw = 0;
         if (c->d_dists) (void)hipFree(c->d_dists);
@@ -685,19 +677,16 @@ int match_impl(pmx_ctx* c, const T* Titer, int knn, double maxDist, uint64_t* vi
         c->d_dists = nullptr;
         c->d_ids = nullptr;
         c->d_w = nullptr;
-        int rc;
         if ((rc = ensure(c, &c->d_dists, &capd, sizeof(T) * (n > 0 ? n : 1)))) return rc;
         if ((rc = ensure(c, (void**)&c->d_ids, &capi, sizeof(int32_t) * (n > 0 ? n : 1)))) return rc;
         if ((rc = ensure(c, &c->d_w, &capw, sizeof(T) * (n > 0 ? n : 1)))) return rc;
         c->match_cap = n;
         c->safe_valid = false;
-        (void)cap;
     }
     if (c->reuse_on && (c->safe_cap < c->N || !c->d_safe)) {
         if (c->d_safe) (void)hipFree(c->d_safe);
         c->d_safe = nullptr;
         size_t caps = 0;
-        int rc;
         if ((rc = ensure(c, &c->d_safe, &caps, tsize(c) * (size_t)std::max<int64_t>(c->N, 1)))) return rc;
         c->safe_cap = std::max<int64_t>(c->N, 1);
         c->safe_valid = false;
@@ -709,11 +698,194 @@ int match_impl(pmx_ctx* c, const T* Titer, int knn, double maxDist, uint64_t* vi
         if (c->d_part_i) (void)hipFree(c->d_part_i);
         c->d_part_d = nullptr;
         c->d_part_i = nullptr;
-        int rc;
         if ((rc = ensure(c, &c->d_part_d, &a, sizeof(T) * pe))) return rc;
         if ((rc = ensure(c, (void**)&c->d_part_i, &b, sizeof(int32_t) * pe))) return rc;
         c->part_cap = pe;
     }
+    return PMX_OK;
+}
+
+// brute force over the whole reference (searchType 0, or no grid yet)
+template <typename T>
+int match_brute(pmx_ctx* c, const Mat4<T>& Tm, int knn, T maxR2, hipEvent_t e0, hipEvent_t e1) {
+    // reset the per-iteration error word and the pair / fallback counters
+    // ([kBlkVisited, kBlkVisited + 16)); the grid match's counter-sum kernel
+    // does both itself, which saves a fill launch per iteration
+    HIPCHK(c, hipMemsetAsync((char*)c->d_result + kBlkIterErr, 0, kBlkVisited + 16 - kBlkIterErr, c->stream));
+    if (knn > kLaneMaxK) {  // (the wave-per-query search over the whole reference, pmx_knn_wide.hip)
+        if (e0) (void)hipEventRecord(e0, c->stream);
+        launch_knn_wide<T>((const P4<T>*)c->d_ref, nullptr, nullptr, nullptr, c->M, (const P4<T>*)c->d_rd, c->N, Tm,
+                           knn, maxR2, nullptr, (T*)c->d_dists, c->d_ids, nullptr, nullptr, nullptr, nullptr,
+                           c->stream);
+        if (e1) (void)hipEventRecord(e1, c->stream);
+    } else {
+        launch_match<T>((const P4<T>*)c->d_ref, c->M_pad, (const P4<T>*)c->d_rd, c->N, Tm, knn, maxR2,
+                        (T*)c->d_dists, c->d_ids, (T*)c->d_part_d, c->d_part_i, c->part_cap, c->stream, e0, e1,
+                        c->cu_count);
+    }
+    if (c->has_radii) launch_apply_radii<T>((T*)c->d_dists, c->d_ids, (const T*)c->d_radii, c->N, knn, c->stream);
+    c->visited_host = (uint64_t)c->N * (uint64_t)c->M;
+    c->ids_grid = false;
+    c->safe_valid = false;
+    return PMX_OK;
+}
+
+// Development profile of the cold form's waves (option tile_prof=1: 4 words
+// per wave, pmx_grid_tile.inc, summarised on stderr; 2: also raw to tile_prof.bin)
+int tile_prof_report(pmx_ctx* c, unsigned long long* prof_buf, int64_t nw) {
+    std::vector<unsigned long long> h((size_t)(4 * nw));
+    HIPCHK(c, hipMemcpyAsync(h.data(), prof_buf, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    set_tile_prof(nullptr);
+    (void)hipFree(prof_buf);
+    std::vector<double> dur((size_t)nw);
+    unsigned long long t0 = ~0ull, t1 = 0;
+    double rsum = 0, csum = 0, fb = 0;
+    for (int64_t w = 0; w < nw; ++w) {
+        dur[(size_t)w] = (double)(h[4 * w + 1] - h[4 * w]) * 0.01;  // (100 MHz: us)
+        t0 = std::min(t0, h[4 * w]);
+        t1 = std::max(t1, h[4 * w + 1]);
+        rsum += (double)(h[4 * w + 2] & 0xffffffffull);
+        fb += (double)(h[4 * w + 2] >> 32);
+        csum += (double)(h[4 * w + 3] & 0xffffffffull);
+    }
+    std::vector<double> sd = dur;
+    std::sort(sd.begin(), sd.end());
+    auto q = [&](double f) { return sd[(size_t)std::min<double>((double)(nw - 1), f * (double)nw)]; };
+    double tot = 0;
+    for (double d : dur) tot += d;
+    // the last-started waves: how long after the kernel's start they began and ran
+    int64_t last = 0;
+    for (int64_t w = 0; w < nw; ++w)
+        if (h[4 * w] > h[4 * last]) last = w;
+    std::fprintf(stderr,
+                 "tile_prof waves %lld span %.1f us  wave us: mean %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f"
+                 "  sum %.0f us  rounds/wave %.2f  points copied/wave %.0f  fallback lanes %.0f"
+                 "  last-started wave at %.1f us ran %.1f us\n",
+                 (long long)nw, (double)(t1 - t0) * 0.01, tot / (double)nw, q(0.5), q(0.9), q(0.99), sd.back(), tot,
+                 rsum / (double)nw, csum / (double)nw, fb, (double)(h[4 * last] - t0) * 0.01, dur[(size_t)last]);
+    // the waves that handed lanes to the per-lane fallback walk, and the
+    // waves over 150 us with how many of them fell back
+    double fsum = 0, fmax = 0, nmax = 0;
+    int64_t fcnt = 0, over = 0, over_fb = 0;
+    for (int64_t w = 0; w < nw; ++w) {
+        const bool fell = (h[4 * w + 2] >> 32) > 0;
+        if (fell) {
+            ++fcnt;
+            fsum += dur[(size_t)w];
+            fmax = std::max(fmax, dur[(size_t)w]);
+        } else {
+            nmax = std::max(nmax, dur[(size_t)w]);
+        }
+        if (dur[(size_t)w] > 150.0) {
+            ++over;
+            over_fb += fell ? 1 : 0;
+        }
+    }
+    std::fprintf(stderr,
+                 "tile_prof fallback waves %lld mean %.1f us max %.1f us; other waves max %.1f us; "
+                 "waves over 150 us %lld (%lld with fallback)\n",
+                 (long long)fcnt, fcnt ? fsum / (double)fcnt : 0.0, fmax, nmax, (long long)over, (long long)over_fb);
+    if (c->tile_prof_raw) {
+        if (FILE* f = std::fopen("tile_prof.bin", "wb")) {
+            std::fwrite(h.data(), 8, h.size(), f);
+            std::fclose(f);
+        }
+    }
+    // duration by dispatch decile
+    for (int dcl = 0; dcl < 10; ++dcl) {
+        double s2 = 0;
+        int64_t a = nw * dcl / 10, b = nw * (dcl + 1) / 10;
+        for (int64_t w = a; w < b; ++w) s2 += dur[(size_t)w];
+        std::fprintf(stderr, "tile_prof decile %d mean %.1f us\n", dcl, s2 / (double)std::max<int64_t>(b - a, 1));
+    }
+    return PMX_OK;
+}
+
+// Several ranks: the segments the counter sum packed are all-gathered (in place:
+// a rank's segment is its block of the gathered array); every rank picks from the union.
+template <typename T>
+int exchange_window(pmx_ctx* c, SpecSel* spec, unsigned long long* xseg) {
+    if (c->N <= 0)  // (no match kernel ran: an empty segment)
+        HIPCHK(c, hipMemsetAsync(xseg, 0, kSpecXHdr * sizeof(unsigned long long), c->stream));
+    int rc = coll_allgather(c, xseg, c->d_specx, kSpecXStride * sizeof(unsigned long long));
+    if (rc) return rc;
+    const bool force = c->enq_iter >= 0 && std::find(c->debug_force_miss.begin(), c->debug_force_miss.end(),
+                                                     c->enq_iter) != c->debug_force_miss.end();
+    launch_spec_pick<T>(c->d_specx, c->nranks, spec, c->d_sel, loop_on_ctl(c), c->shard_async ? 1 : 0, force ? 1 : 0,
+                        c->stream);
+    c->spec_exchanged = true;
+    return PMX_OK;
+}
+
+// The grid match: the facts of this context -> the plan (pmx_match_plan.h) ->
+// the kernels' arguments -> the launch; then the bookkeeping, from the plan.
+template <typename T>
+int match_grid(pmx_ctx* c, const Mat4<T>& Tm, int knn, T maxR2, hipEvent_t e0, hipEvent_t e1) {
+    // a reading's first match runs on the cold level; any other match
+    // may use the finer levels the side stream builds
+    if (c->side_pending && (c->have_match || c->level != cold_level(c))) side_join(c);
+    const GridLevel& L = c->lv(c->level);
+    SpecSel* spec = c->spec_now();
+    // the previous match of this reading: its ids are positions in the level
+    // it ran on (in loop mode the kernels take that level from LoopCtl)
+    const MatchFacts f{c->grid_mode, knn, c->N, c->reuse_on, c->nbr_on, c->safe_valid, c->have_match, c->ids_grid,
+                       c->knn, c->ids_level == c->level, c->nbr_prev, L.gpn != nullptr, c->loop_on,
+                       c->loop_dev.tile_dispatch != 0, spec != nullptr, c->merge_counter || c->step_counter,
+                       c->d_vpart != nullptr};
+    const GridMatchPlan plan = plan_grid_match(f);
+
+    GridDesc<T> D = level_desc<T>(L);
+    if (!plan.nbr_normals) D.gpn = nullptr;
+    MatchQuery<T> Q{(const P4<T>*)c->d_rd, c->N, Tm, knn, maxR2, c->has_radii ? (const T*)c->d_radii : nullptr,
+                    c->d_waves, c->n_waves, c->tile_max};
+    MatchOut<T> O{(T*)c->d_dists, c->d_ids, c->d_vpart, c->d_visited, c->d_iter_err};
+    if (plan.reuse) {
+        O.safe = (T*)c->d_safe;
+        Q.coop_max = c->coop_max;
+        for (int i = 0; i < 16; ++i) Q.Tprev.m[i] = (T)c->Tprev[i];
+    }
+    if (plan.nbr) {
+        int rc = ensure(c, &c->d_nbr, &c->nbr_bytes, 2 * sizeof(P4<T>) * (size_t)std::max<int64_t>(c->N, 1));
+        if (rc) return rc;
+        O.nbr = (P4<T>*)c->d_nbr;
+    }
+    c->nbr_prev = plan.nbr_prev;
+    c->nbr_normals = plan.nbr_normals;
+    // several ranks: the counter sum packs this rank's window segment
+    // (d_specx is allocated by a loop_begin on a sharded context: a window
+    // switched on before the context became sharded has none)
+    c->spec_exchanged = false;
+    if (spec && sharded(c)) {
+        if (!c->d_specx)
+            HIPCHK(c, hipMalloc((void**)&c->d_specx, sizeof(unsigned long long) * kSpecXStride * c->nranks));
+        O.xseg = c->d_specx + (size_t)kSpecXStride * c->rank;
+    }
+    unsigned long long* prof_buf = nullptr;
+    const int64_t nw = (c->N + 63) / 64;
+    if (c->tile_prof && plan.form == MatchForm::ColdTile) {
+        HIPCHK(c, hipMalloc((void**)&prof_buf, sizeof(unsigned long long) * 4 * std::max<int64_t>(nw, 1)));
+        set_tile_prof(prof_buf);
+    }
+    launch_grid_match<T>(plan, D, Q, O, loop_ctl(c), (const GridDesc<T>*)c->d_gdesc, spec, c->d_sel, e0, e1, c->stream);
+    int rc = PMX_OK;
+    if (prof_buf && (rc = tile_prof_report(c, prof_buf, nw))) return rc;
+    if (O.xseg && (rc = exchange_window<T>(c, spec, O.xseg))) return rc;
+    c->safe_valid = plan.safe_valid;
+    c->visited_host = 0;
+    c->ids_grid = true;
+    c->ids_level = c->level;
+    return PMX_OK;
+}
+
+template <typename T>
+int match_impl(pmx_ctx* c, const T* Titer, int knn, double maxDist, uint64_t* visited) {
+    if (!c->d_ref) return fail(c, PMX_E_STATE, "no reference (Matcher::init not called)");
+    if (!c->d_rd && c->N > 0) return fail(c, PMX_E_STATE, "no reading");
+    if (knn < 1) return fail(c, PMX_E_BAD_PARAM, "knn must be >= 1");
+    if (!(maxDist >= 0)) return fail(c, PMX_E_BAD_PARAM, "maxDist must be >= 0");
+    int rc = match_room<T>(c, knn);
+    if (rc) return rc;
     Mat4<T> Tm = embed<T>(Titer, c->rows);
     for (int i = 0; i < 16; ++i) {
         c->Tprev[i] = c->Tstep[i];  // (the previous match's: its warm start)
@@ -721,184 +893,13 @@ int match_impl(pmx_ctx* c, const T* Titer, int knn, double maxDist, uint64_t* vi
     }
     const T md = (T)maxDist;
     const T maxR2 = md * md;  // libnabo squares the radius in T [ext]
-    // reset the per-iteration error word and the pair / fallback counters
-    // ([kBlkVisited, kBlkVisited + 16)); the grid match's counter-sum kernel
-    // does both itself, which saves a fill launch per iteration
-    const bool grid = !(c->search_type == 0 || !c->grid_ready);
-    if (!grid)
-        HIPCHK(c, hipMemsetAsync((char*)c->d_result + kBlkIterErr, 0, kBlkVisited + 16 - kBlkIterErr, c->stream));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing) {
         e0 = get_event(c);
         e1 = get_event(c);
     }
-    if (c->search_type == 0 || !c->grid_ready) {
-        if (knn > kLaneMaxK) {  // (the wave-per-query search over the whole reference, pmx_knn_wide.hip)
-            if (e0) (void)hipEventRecord(e0, c->stream);
-            launch_knn_wide<T>((const P4<T>*)c->d_ref, nullptr, nullptr, nullptr, c->M, (const P4<T>*)c->d_rd, c->N,
-                               Tm, knn, maxR2, nullptr, (T*)c->d_dists, c->d_ids, nullptr, nullptr, nullptr, nullptr,
-                               c->stream);
-            if (e1) (void)hipEventRecord(e1, c->stream);
-        } else {
-            launch_match<T>((const P4<T>*)c->d_ref, c->M_pad, (const P4<T>*)c->d_rd, c->N, Tm, knn, maxR2,
-                            (T*)c->d_dists, c->d_ids, (T*)c->d_part_d, c->d_part_i, c->part_cap, c->stream, e0, e1,
-                            c->cu_count);
-        }
-        if (c->has_radii)
-            launch_apply_radii<T>((T*)c->d_dists, c->d_ids, (const T*)c->d_radii, c->N, knn, c->stream);
-        c->visited_host = (uint64_t)c->N * (uint64_t)c->M;
-        c->ids_grid = false;
-        c->safe_valid = false;
-    } else {
-        // a reading's first match runs on the cold level; any other match
-        // may use the finer levels the side stream builds
-        if (c->side_pending && (c->have_match || c->level != cold_level(c))) side_join(c);
-        const GridLevel& L = c->lv(c->level);
-        // warm start from the previous match of the same reading (same k):
-        // its ids are positions in the level it ran on (in loop mode the
-        // kernel takes that level from LoopCtl.hint_level)
-        // temporal reuse: the output buffers hold this reading's previous
-        // match (same k, same level) with its safe radii
-        GridReuse<T> ru;
-        const bool no_prev = !(c->safe_valid && c->have_match && c->ids_grid && c->knn == knn);
-        if (c->reuse_on && c->grid_mode >= 1 && knn <= kLaneMaxK) {  // (the wide search keeps no safe radii)
-            ru.mode = !no_prev && c->ids_level == c->level ? 2 : 1;
-            ru.safe = (T*)c->d_safe;
-            ru.coop_max = c->coop_max;
-            for (int i = 0; i < 16; ++i) ru.Tprev.m[i] = (T)c->Tprev[i];
-            if (knn == 1 && c->nbr_on && (ru.mode != 2 || c->nbr_prev || c->loop_on) &&
-                       !(c->loop_on && c->loop_dev.tile_dispatch)) {
-                // (a reuse match reads the records only if the last match
-                // wrote them; a device-loop match decides reuse on the device,
-                // where every match of the loop writes them.  Not for dense
-                // readings, tile dispatch: most queries miss there, and the
-                // records' writes cost more than the certificate saves, C5
-                // 1.51 vs 1.47 ms/iteration)
-                int rc = ensure(c, &c->d_nbr, &c->nbr_bytes, 2 * sizeof(P4<T>) * (size_t)std::max<int64_t>(c->N, 1));
-                if (rc) return rc;
-                ru.nbr = (P4<T>*)c->d_nbr;
-                ru.gpn = (const P4<T>*)L.gpn;
-            }
-        }
-        c->nbr_prev = ru.nbr != nullptr;
-        c->nbr_normals = ru.gpn != nullptr;
-        // several ranks: the counter sum packs this rank's window segment,
-        // the segments are all-gathered and every rank picks from the union
-        SpecSel* spec = c->spec_now();
-        c->spec_exchanged = false;
-        // (this rank's segment is its block of the gathered array: an in-place all-gather)
-        // (d_specx is allocated by a loop_begin on a sharded context: a window
-        // switched on before the context became sharded has none)
-        if (spec && sharded(c) && !c->d_specx)
-            HIPCHK(c, hipMalloc((void**)&c->d_specx, sizeof(unsigned long long) * kSpecXStride * c->nranks));
-        unsigned long long* xseg = spec && sharded(c) ? c->d_specx + (size_t)kSpecXStride * c->rank : nullptr;
-        const bool cold_now = no_prev && c->reuse_on;
-        // (development profile of the cold form's waves, option tile_prof=1:
-        // per wave duration, rounds and points copied, summarised on stderr)
-        const bool tile_prof = c->tile_prof;
-        unsigned long long* prof_buf = nullptr;
-        const int64_t nw = (c->N + 63) / 64;
-        if (tile_prof && cold_now) {
-            HIPCHK(c, hipMalloc((void**)&prof_buf, sizeof(unsigned long long) * 4 * std::max<int64_t>(nw, 1)));
-            set_tile_prof(prof_buf);
-        }
-        launch_grid_match<T>(c->grid_mode, (const P4<T>*)L.gpts, L.gidx, L.gstart, L.lo, L.h, L.dim,
-                             (const P4<T>*)c->d_rd, c->N, c->d_waves, c->n_waves, Tm, knn, maxR2, c->tile_max,
-                             (T*)c->d_dists, c->d_ids, c->d_vpart, c->merge_counter || c->step_counter ? nullptr : c->d_visited,
-                             c->d_iter_err, ru, loop_ctl(c),
-                             (const GridDesc<T>*)c->d_gdesc, spec, c->d_sel, xseg,
-                             c->has_radii ? (const T*)c->d_radii : nullptr, cold_now,
-                             c->loop_on && c->loop_dev.tile_dispatch, e0, e1, c->stream);
-        if (prof_buf) {
-            std::vector<unsigned long long> h((size_t)(4 * nw));
-            HIPCHK(c, hipMemcpyAsync(h.data(), prof_buf, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            set_tile_prof(nullptr);
-            (void)hipFree(prof_buf);
-            std::vector<double> dur((size_t)nw);
-            unsigned long long t0 = ~0ull, t1 = 0;
-            double rsum = 0, csum = 0, fb = 0;
-            for (int64_t w = 0; w < nw; ++w) {
-                dur[(size_t)w] = (double)(h[4 * w + 1] - h[4 * w]) * 0.01;  // (100 MHz: us)
-                t0 = std::min(t0, h[4 * w]);
-                t1 = std::max(t1, h[4 * w + 1]);
-                rsum += (double)(h[4 * w + 2] & 0xffffffffull);
-                fb += (double)(h[4 * w + 2] >> 32);
-                csum += (double)(h[4 * w + 3] & 0xffffffffull);
-            }
-            std::vector<double> sd = dur;
-            std::sort(sd.begin(), sd.end());
-            auto q = [&](double f) { return sd[(size_t)std::min<double>((double)(nw - 1), f * (double)nw)]; };
-            double tot = 0;
-            for (double d : dur) tot += d;
-            // the last-started waves: how long after the kernel's start they began and ran
-            int64_t last = 0;
-            for (int64_t w = 0; w < nw; ++w)
-                if (h[4 * w] > h[4 * last]) last = w;
-            std::fprintf(stderr,
-                         "tile_prof waves %lld span %.1f us  wave us: mean %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f"
-                         "  sum %.0f us  rounds/wave %.2f  points copied/wave %.0f  fallback lanes %.0f"
-                         "  last-started wave at %.1f us ran %.1f us\n",
-                         (long long)nw, (double)(t1 - t0) * 0.01, tot / (double)nw, q(0.5), q(0.9), q(0.99),
-                         sd.back(), tot, rsum / (double)nw, csum / (double)nw, fb, (double)(h[4 * last] - t0) * 0.01,
-                         dur[(size_t)last]);
-            // the waves that handed lanes to the per-lane fallback walk
-            {
-                double fsum = 0, fmax = 0, nmax = 0;
-                int64_t fcnt = 0;
-                for (int64_t w = 0; w < nw; ++w) {
-                    if ((h[4 * w + 2] >> 32) > 0) {
-                        ++fcnt;
-                        fsum += dur[(size_t)w];
-                        fmax = std::max(fmax, dur[(size_t)w]);
-                    } else {
-                        nmax = std::max(nmax, dur[(size_t)w]);
-                    }
-                }
-                int64_t over = 0;  // waves over 150 us, and how many of them fell back
-                int64_t over_fb = 0;
-                for (int64_t w = 0; w < nw; ++w)
-                    if (dur[(size_t)w] > 150.0) {
-                        ++over;
-                        over_fb += (h[4 * w + 2] >> 32) > 0 ? 1 : 0;
-                    }
-                std::fprintf(stderr,
-                             "tile_prof fallback waves %lld mean %.1f us max %.1f us; other waves max %.1f us; "
-                             "waves over 150 us %lld (%lld with fallback)\n",
-                             (long long)fcnt, fcnt ? fsum / (double)fcnt : 0.0, fmax, nmax, (long long)over,
-                             (long long)over_fb);
-            }
-            // (tile_prof=2: the raw per-wave words to tile_prof.bin in the working directory)
-            if (c->tile_prof_raw) {
-                if (FILE* f = std::fopen("tile_prof.bin", "wb")) {
-                    std::fwrite(h.data(), 8, h.size(), f);
-                    std::fclose(f);
-                }
-            }
-            // duration by dispatch decile
-            for (int dcl = 0; dcl < 10; ++dcl) {
-                double s2 = 0;
-                int64_t a = nw * dcl / 10, b = nw * (dcl + 1) / 10;
-                for (int64_t w = a; w < b; ++w) s2 += dur[(size_t)w];
-                std::fprintf(stderr, "tile_prof decile %d mean %.1f us\n", dcl, s2 / (double)std::max<int64_t>(b - a, 1));
-            }
-        }
-        if (xseg) {
-            if (c->N <= 0)  // (no match kernel ran: an empty segment)
-                HIPCHK(c, hipMemsetAsync(xseg, 0, kSpecXHdr * sizeof(unsigned long long), c->stream));
-            int rc = coll_allgather(c, xseg, c->d_specx, kSpecXStride * sizeof(unsigned long long));
-            if (rc) return rc;
-            const bool force = c->enq_iter >= 0 && std::find(c->debug_force_miss.begin(), c->debug_force_miss.end(),
-                                                             c->enq_iter) != c->debug_force_miss.end();
-            launch_spec_pick<T>(c->d_specx, c->nranks, spec, c->d_sel, loop_on_ctl(c), c->shard_async ? 1 : 0,
-                                force ? 1 : 0, c->stream);
-            c->spec_exchanged = true;
-        }
-        c->safe_valid = ru.mode != 0;
-        c->visited_host = 0;
-        c->ids_grid = true;
-        c->ids_level = c->level;
-    }
+    const bool grid = c->search_type != 0 && c->grid_ready;
+    if ((rc = grid ? match_grid<T>(c, Tm, knn, maxR2, e0, e1) : match_brute<T>(c, Tm, knn, maxR2, e0, e1))) return rc;
     HIPCHK(c, hipGetLastError());
     if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
     c->knn = knn;

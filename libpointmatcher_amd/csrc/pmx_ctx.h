@@ -132,7 +132,7 @@ struct pmx_ctx {
     int64_t safe_cap = 0;
     int tile_dispatch_req = -1;   // tile dispatch in the device loop: -1 auto (reading >= 4x the reference), 0 off, 1 on (option tile_dispatch)
     int coop_max = 4;             // wave-cooperative full searches for blocks with <= this many misses (option coop_max)
-    // k = 1 neighbour records (GridReuse::nbr): P4<T>[N]; nbr_prev: the last
+    // k = 1 neighbour records (MatchOut::nbr): P4<T>[N]; nbr_prev: the last
     // match wrote them (option nbr_cache=0: off)
     void* d_nbr = nullptr;
     size_t nbr_bytes = 0;

@@ -343,7 +343,7 @@ __device__ __forceinline__ void write_out(int64_t j, int k, T maxR2, const T (&k
     }
 }
 
-// k = 1 neighbour record (GridReuse::nbr): the point the k-list holds, with
+// k = 1 neighbour record (MatchOut::nbr): the point the k-list holds, with
 // the id write_out stores (-1: none, or beyond the radius) in w
 // (gpn: the level's interleaved point / normal records — the normal then
 // goes to nbr[N + j], what the point-to-plane reduction reads)
@@ -965,108 +965,76 @@ __global__ __launch_bounds__(256, (LaneWaves<T, KT>::value)) void grid_lane_kern
 // ------------------------------------------------------------ tile kernel --
 #include "pmx_grid_tile.inc"
 
+// One list size's launches.  (timing: e0 / e1 are recorded by the dispatch
+// itself — the first launch's start, the last launch's end —
+// hipExtLaunchKernelGGL, the kernel's own execution as a rocprofv3 kernel
+// trace counts it; null events record nothing)
 template <typename T, int KT>
-static void launch_kt(int mode, const P4<T>* gpts, const int32_t* gidx, const uint32_t* start, const GridGeom& G,
-                      const P4<T>* rd, int64_t N, const uint32_t* waves, int64_t n_waves, const Mat4<T>& Tm, int knn,
-                      T maxR2, uint32_t max_pts, T* dists, int32_t* ids, unsigned long long* visited,
-                      const GridReuse<T>& ru, const LoopCtl* ctl, const GridDesc<T>* gd, SpecSel* spec,
-                      const T* radii, bool cold, bool tile_disp, hipEvent_t e0, hipEvent_t e1, hipStream_t s) {
-    // (timing: e0 / e1 are recorded by the dispatch itself — the first
-    // launch's start, the last launch's end — hipExtLaunchKernelGGL, the
-    // kernel's own execution as a rocprofv3 kernel trace counts it; null
-    // events record nothing)
-    if (cold) {  // a new reading's first match: the tile kernel's cold form (pmx_grid_tile.inc)
-        hipExtLaunchKernelGGL((grid_tile_kernel<T, KT>), dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, e0, e1, 0,
-                              gpts, gidx, start, G, rd, N, (const uint32_t*)nullptr, Tm, knn, maxR2, max_pts, dists,
-                              ids, visited, radii, 1, ctl, gd, spec, ru.safe, ru.nbr, ru.gpn);
-    } else if (mode >= 1) {  // the per-lane shell search
-        const bool both = tile_disp && ctl && ru.mode;
-        if (both)  // (device loop: the step picks one of the two forms)
-            hipExtLaunchKernelGGL((grid_tile_kernel<T, KT>), dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, e0,
-                                  (hipEvent_t) nullptr, 0, gpts, gidx, start, G, rd, N, (const uint32_t*)nullptr, Tm,
-                                  knn, maxR2, max_pts, dists, ids, visited, radii, 2, ctl, gd, spec, ru.safe,
-                                  ru.nbr, ru.gpn);
-        constexpr int Q = LaneQ<KT>::value;
-        const int64_t grid = (N + 256 * Q - 1) / (256 * Q);
-        hipExtLaunchKernelGGL((grid_lane_kernel<T, KT, Q>), dim3((unsigned)grid), dim3(256), 0, s,
-                              both ? (hipEvent_t) nullptr : e0, e1, 0, gpts, gidx, start, G, rd, N, Tm, knn, maxR2,
-                              dists, ids, visited, ru.mode, ru.safe, ru.Tprev, ctl, gd, spec, radii, ru.coop_max,
-                              ru.nbr, ru.gpn);
-    } else {
-        const int64_t W = waves ? n_waves : (N + 63) / 64;
-        hipExtLaunchKernelGGL((grid_tile_kernel<T, KT>), dim3((unsigned)W), dim3(64), 0, s, e0, e1, 0, gpts, gidx,
-                              start, G, rd, N, waves, Tm, knn, maxR2, max_pts, dists, ids, visited, radii, 0,
-                              (const LoopCtl*)nullptr, (const GridDesc<T>*)nullptr, (SpecSel*)nullptr, (T*)nullptr,
-                              (P4<T>*)nullptr, (const P4<T>*)nullptr);
-    }
+static void launch_lists(const GridMatchPlan& plan, const GridDesc<T>& D, const MatchQuery<T>& Q, const MatchOut<T>& O,
+                         const LoopCtl* ctl, const GridDesc<T>* gd, SpecSel* spec, hipEvent_t e0, hipEvent_t e1,
+                         hipStream_t s) {
+    const hipEvent_t none = nullptr;
+    // the tile kernel: the table form takes the host's transform and level and
+    // the reading's wave table; the others 64-slot chunks and the device loop
+    auto tile = [&](TileForm f, hipEvent_t a, hipEvent_t b) {
+        const bool tab = f == kTileTable;
+        const int64_t W = tab && Q.waves ? Q.n_waves : (Q.N + 63) / 64;
+        hipExtLaunchKernelGGL((grid_tile_kernel<T, KT>), dim3((unsigned)W), dim3(64), 0, s, a, b, 0, D.gpts, D.gidx,
+                              D.start, D.G, Q.rd, Q.N, tab ? Q.waves : nullptr, Q.Tm, Q.k, Q.maxR2, Q.max_pts, O.dists,
+                              O.ids, O.vpart, Q.radii, f, tab ? nullptr : ctl, tab ? nullptr : gd, spec, O.safe, O.nbr,
+                              D.gpn);
+    };
+    if (plan.form == MatchForm::TableTile) return tile(kTileTable, e0, e1);
+    if (plan.form == MatchForm::ColdTile) return tile(kTileCold, e0, e1);
+    const bool both = plan.form == MatchForm::LaneAndWarmTile;  // (LoopCtl::use_tile lets one of the two run)
+    if (both) tile(kTileWarm, e0, none);
+    constexpr int LQ = LaneQ<KT>::value;
+    hipExtLaunchKernelGGL((grid_lane_kernel<T, KT, LQ>), dim3((unsigned)((Q.N + 256 * LQ - 1) / (256 * LQ))), dim3(256), 0,
+                          s, both ? none : e0, e1, 0, D.gpts, D.gidx, D.start, D.G, Q.rd, Q.N, Q.Tm, Q.k, Q.maxR2, O.dists,
+                          O.ids, O.vpart, plan.reuse, O.safe, Q.Tprev, ctl, gd, spec, Q.radii, Q.coop_max, O.nbr, D.gpn);
 }
 
 // option tile_prof: the cold form's per-wave profile into buf (4 words per wave)
 void set_tile_prof(unsigned long long* buf) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tile_prof), &buf, sizeof(buf)); }
 
 template <typename T>
-void launch_grid_match(int mode, const P4<T>* gpts, const int32_t* gidx, const uint32_t* start, const double* lo,
-                       double h, const int* g, const P4<T>* rd, int64_t N, const uint32_t* waves, int64_t n_waves,
-                       const Mat4<T>& Tm, int knn, T maxR2, uint32_t max_pts, T* dists, int32_t* ids,
-                       unsigned long long* visited, unsigned long long* vout, int* iter_err,
-                       const GridReuse<T>& ru, const LoopCtl* ctl, const GridDesc<T>* gd, SpecSel* spec,
-                       SelectState* spec_st, unsigned long long* xseg, const T* radii, bool cold, bool tile_disp,
+void launch_grid_match(const GridMatchPlan& plan, const GridDesc<T>& D, const MatchQuery<T>& Q, const MatchOut<T>& O,
+                       const LoopCtl* ctl, const GridDesc<T>* gd, SpecSel* spec, SelectState* spec_st,
                        hipEvent_t ev_start, hipEvent_t ev_end, hipStream_t s) {
-    if (N <= 0) return;
-    cold = cold && mode >= 1;
-    if (mode < 1 || !visited) spec = nullptr;  // (the window needs the per-lane kernel and the counters)
-    GridGeom G;
-    for (int a = 0; a < 3; ++a) {
-        G.lo[a] = lo[a];
-        G.g[a] = g[a];
-    }
-    G.h = h;
-    G.inv_h = 1.0 / h;
-    if (knn > kLaneMaxK) {  // a k-list spread over a wave per query (pmx_knn_wide.hip; no reuse)
+    if (!plan.run) return;
+    if (!plan.window) spec = nullptr;
+    if (plan.form == MatchForm::Wide) {  // a k-list spread over a wave per query (pmx_knn_wide.hip; no reuse)
         if (ev_start) (void)hipEventRecord(ev_start, s);
-        launch_knn_wide<T>(gpts, gidx, start, &G, 0, rd, N, Tm, knn, maxR2, radii, dists, ids, visited, ctl, gd, spec,
-                           s);
+        launch_knn_wide<T>(D.gpts, D.gidx, D.start, &D.G, 0, Q.rd, Q.N, Q.Tm, Q.k, Q.maxR2, Q.radii, O.dists, O.ids,
+                           O.vpart, ctl, gd, spec, s);
         if (ev_end) (void)hipEventRecord(ev_end, s);
     } else {
 #define PMX_KT(KT) \
-    launch_kt<T, KT>(mode, gpts, gidx, start, G, rd, N, waves, n_waves, Tm, knn, maxR2, max_pts, dists, ids, visited, \
-                     ru, ctl, gd, spec, radii, cold, tile_disp, ev_start, ev_end, s)
-        // with reuse the list keeps room for the (k+1)-th point (the safe radius;
-        // the cold tile writes radius 0 and keeps k entries)
-        const int kl = ru.mode && mode >= 1 && knn < 16 && !cold ? knn + 1 : knn;
-        if (kl == 1)
+    case KT:       \
+        launch_lists<T, KT>(plan, D, Q, O, ctl, gd, spec, ev_start, ev_end, s); \
+        break
+        switch (plan.kt) {
             PMX_KT(1);
-        else if (kl <= 2)
             PMX_KT(2);
-        else if (kl <= 4)
             PMX_KT(4);
-        else if (kl <= 5)
-            PMX_KT(5);  // (k = 4 with the (k+1)-th entry: 5 fit the 128-VGPR budget, 8 spilled)
-        else if (kl <= 8)
+            PMX_KT(5);
             PMX_KT(8);
-        else
             PMX_KT(16);
+        }
 #undef PMX_KT
     }
-    if (visited && vout)
-        hipLaunchKernelGGL(counter_sum_kernel<T>, dim3(1), dim3(kVSlots), 0, s, visited, vout, iter_err, ctl, spec,
-                           spec_st, xseg);
+    if (plan.counter_sum)
+        hipLaunchKernelGGL(counter_sum_kernel<T>, dim3(1), dim3(kVSlots), 0, s, O.vpart, O.vout, O.iter_err, ctl, spec,
+                           spec_st, O.xseg);
 }
 
-template void launch_grid_match<float>(int, const P4<float>*, const int32_t*, const uint32_t*, const double*, double,
-                                       const int*, const P4<float>*, int64_t, const uint32_t*, int64_t,
-                                       const Mat4<float>&, int, float, uint32_t, float*, int32_t*,
-                                       unsigned long long*, unsigned long long*, int*, const GridReuse<float>&,
-                                       const LoopCtl*, const GridDesc<float>*, SpecSel*, SelectState*,
-                                       unsigned long long*, const float*, bool, bool, hipEvent_t, hipEvent_t,
-                                       hipStream_t);
-template void launch_grid_match<double>(int, const P4<double>*, const int32_t*, const uint32_t*, const double*, double,
-                                        const int*, const P4<double>*, int64_t, const uint32_t*, int64_t,
-                                        const Mat4<double>&, int, double, uint32_t, double*, int32_t*,
-                                        unsigned long long*, unsigned long long*, int*, const GridReuse<double>&,
-                                        const LoopCtl*, const GridDesc<double>*, SpecSel*, SelectState*,
-                                        unsigned long long*, const double*, bool, bool, hipEvent_t, hipEvent_t,
-                                        hipStream_t);
+#define PMX_INST(T)                                                                                           \
+    template void launch_grid_match<T>(const GridMatchPlan&, const GridDesc<T>&, const MatchQuery<T>&,        \
+                                       const MatchOut<T>&, const LoopCtl*, const GridDesc<T>*, SpecSel*,      \
+                                       SelectState*, hipEvent_t, hipEvent_t, hipStream_t)
+PMX_INST(float);
+PMX_INST(double);
+#undef PMX_INST
 
 // map match ids (grid positions, -1 = none) back to reference indices
 __global__ void pos_to_index_kernel(const int32_t* __restrict__ pos, const int32_t* __restrict__ gidx,

@@ -12,7 +12,7 @@
 // `max_pts` points (or 1024 rows) hands its uncertified lanes to the
 // per-lane shell search.
 //
-// Cold form (`cold` = 1): the first match of a new reading inside the
+// Cold form (kTileCold): the first match of a new reading inside the
 // per-lane default mode (nothing to reuse yet, and at the initial pose half
 // the queries need shells past the 3x3x3 block, which the per-lane walk pays
 // for in dependent gathers).  It takes the device loop's level and transform,
@@ -129,6 +129,14 @@ __device__ __forceinline__ void tile_scan(const P4<T>* __restrict__ lp, int cnt,
 // real-time stamps, box rounds and points copied; null: off)
 __device__ unsigned long long* g_tile_prof = nullptr;
 
+// which form of the tile kernel a launch runs (a run-time value: one
+// instantiation serves the three)
+enum TileForm : int {
+    kTileTable = 0,  // grid_mode 0: the reading's wave table, no reuse state
+    kTileCold = 1,   // a reading's first match under reuse (above)
+    kTileWarm = 2,   // tile dispatch: a match with a previous one, when LoopCtl::use_tile says so
+};
+
 template <typename T, int KT>
 __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kernel(const P4<T>* __restrict__ gpts,
                                                        const int32_t* __restrict__ gidx,
@@ -138,7 +146,7 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
                                                        T maxR2, uint32_t max_pts, T* __restrict__ out_d,
                                                        int32_t* __restrict__ out_i,
                                                        unsigned long long* __restrict__ visited,
-                                                       const T* __restrict__ radii, int cold,
+                                                       const T* __restrict__ radii, TileForm form,
                                                        const LoopCtl* __restrict__ ctl,
                                                        const GridDesc<T>* __restrict__ gd, SpecSel* __restrict__ spec,
                                                        T* __restrict__ safe, P4<T>* __restrict__ nbr,
@@ -146,7 +154,7 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
     constexpr int CAP = TileCap<T>::value;
     if (ctl) {  // device loop: transform and level from the device
         if (ctl->done) return;
-        if (cold == 2 && !ctl->use_tile) return;  // (tile dispatch: the per-lane kernel runs this match)
+        if (form == kTileWarm && !ctl->use_tile) return;  // (tile dispatch: the per-lane kernel runs this match)
         const GridDesc<T>& D = gd[ctl->level];
         gpts = D.gpts;
         gidx = D.gidx;
@@ -190,7 +198,7 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
         bool qnan;
         cell_of_q(G, q, c, qnan);
         ok = !qnan;
-        if (cold == 2 && safe && ctl && ctl->prev_level == ctl->level) {
+        if (form == kTileWarm && safe && ctl && ctl->prev_level == ctl->level) {
             const T rs = safe[j], dkp = out_d[j * k + k - 1];
             Mat4<T> Tp;
 #pragma unroll
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
         ki[s] = kNoPos;
     }
     uint32_t visits = 0;
-    unsigned long long* prof = cold == 1 ? g_tile_prof : nullptr;
+    unsigned long long* prof = form == kTileCold ? g_tile_prof : nullptr;
     const unsigned long long t_start = prof ? __builtin_amdgcn_s_memrealtime() : 0ull;
     uint32_t copied = 0, nround = 0;
     bool done = !ok;  // lanes without a searchable query are done from the start
@@ -391,10 +399,10 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
     }
     {
         const unsigned long long nfb = __popcll(__ballot(fallback));
-        if (lane == 0 && nfb && visited && !cold) atomicAdd(vslot(visited, 1), nfb);
+        if (lane == 0 && nfb && visited && form == kTileTable) atomicAdd(vslot(visited, 1), nfb);
     }
     if (fallback) {
-        if (cold) visits = 0;  // (a cold fallback lane reports its own walk)
+        if (form != kTileTable) visits = 0;  // (a cold or warm fallback lane reports its own walk)
 #pragma unroll
         for (int s = 0; s < KT; ++s) {
             kd[s] = (T)__builtin_huge_val();
@@ -404,7 +412,7 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
         lane_search<T, KT>(gpts, gidx, start, G, qx, qy, qz, q, c, maxR2, k, kd, ki, visits, lbx);
         lbc = lbx;
     }
-    if (!cold) {
+    if (form == kTileTable) {
         if (active) write_out<T, KT>(j, k, maxR2, kd, ki, out_d, out_i);
         add_visits(visits, visited);
         return;
@@ -416,7 +424,7 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
         // (the cold form keeps k entries: radius 0, the next match searches;
         // the warm form's lists hold the (k+1)-th: the safe radius of the
         // box it was certified in, as a per-lane search leaves it)
-        if (safe) st_out(&safe[j], cold == 2 ? safe_radius<T, KT>(kd, ki, k, lbc) : (T)0);
+        if (safe) st_out(&safe[j], form == kTileWarm ? safe_radius<T, KT>(kd, ki, k, lbc) : (T)0);
         if (safe && k == 1) write_nbr<T, KT>(nbr, gpts, nbr_gpn, N, j, maxR2, kd, ki);
     }
     // lane-search-equivalent visits: the points of the lane's 3x3x3 block
@@ -440,7 +448,7 @@ __global__ __launch_bounds__(64, (TileWaves<T, KT>::value)) void grid_tile_kerne
     {
         // (full searches: every query; the warm form counts the ones the
         // per-lane certificate would have failed)
-        const unsigned long long m = __ballot(active && !(cold == 2 && est_pass));
+        const unsigned long long m = __ballot(active && !(form == kTileWarm && est_pass));
         if (lane == 0 && visited && safe && m) atomicAdd(vslot(visited, 1), (unsigned long long)__popcll(m));
     }
     if (sa.on) spec_acc_flush<T>(sa, vslot(visited, 2), vslot(visited, 3));

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "pmx_match_plan.h"
 #include "pmx_sums.h"
 
 namespace pmx {
@@ -169,23 +170,39 @@ struct LoopCtl {
     double T[16];
     double Tprev[16];  // the step transform of that previous match
 };
-// temporal reuse of the grid match (pmx_grid.hip): mode 0 off, 1 store the
-// safe radii, 2 store and certify from the previous match made at Tprev
+// The two sides of a grid match as match_grid (pmx_chain.hip) hands them to
+// launch_grid_match; the kernels take the fields written out.
 template <typename T>
-struct GridReuse {
-    int mode = 0;
-    T* safe = nullptr;
-    Mat4<T> Tprev{};
-    // a block whose misses are at most this many searches each with a whole
-    // wave (pmx_grid.hip coop_search); more take the per-lane search
+struct MatchQuery {
+    const P4<T>* rd;
+    int64_t N;
+    Mat4<T> Tm;
+    int k;
+    T maxR2;
+    const T* radii;         // per-query radii (KDTreeVarDistMatcher; null: maxR2 for all)
+    const uint32_t* waves;  // the tile kernel: the table form's wave table,
+    int64_t n_waves;
+    uint32_t max_pts;  // and the largest box scanned from LDS
+    // temporal reuse: a block whose misses are at most coop_max searches each
+    // with a whole wave (pmx_grid.hip coop_search), more take the per-lane
+    // search; Tprev is the transform of the previous match (reuse mode 2)
     int coop_max = 0;
+    Mat4<T> Tprev{};
+};
+template <typename T>
+struct MatchOut {
+    T* dists;
+    int32_t* ids;  // positions in the level's gpts (launch_pos_to_index maps them back)
+    unsigned long long *vpart, *vout;  // the spread pair / fallback counters (null: none), and their sum
+    int* iter_err;
+    unsigned long long* xseg = nullptr;  // several ranks: this rank's window segment, packed by the counter sum
+    T* safe = nullptr;                   // safe radii (reuse mode != 0)
     // k = 1: each query's neighbour record (the grid point, its position in
     // w), written by every search that leaves a safe radius, so that the
     // certificate reads it with the query instead of gathering it by id
     // (null: off).  With the level's interleaved point / normal records
-    // (gpn) the normals follow at nbr + N, for the point-to-plane reduction.
+    // (GridDesc::gpn) the normals follow at nbr + N, for the point-to-plane reduction.
     P4<T>* nbr = nullptr;
-    const P4<T>* gpn = nullptr;
 };
 template <typename T>
 __device__ __forceinline__ void ctl_transform(const LoopCtl* ctl, Mat4<T>& Tm) {
@@ -196,7 +213,6 @@ __device__ __forceinline__ void ctl_transform(const LoopCtl* ctl, Mat4<T>& Tm) {
 // k-NN for k > kLaneMaxK (pmx_knn_wide.hip): one wave per query, the k-list
 // spread over the wave.  start == null: brute force over pts[0, M) (ids are
 // indices); otherwise a grid level (ids are positions), G its geometry.
-constexpr int kLaneMaxK = 16;   // the per-lane searches' largest k-list (wider: the wave-per-query search)
 template <typename T>
 void launch_knn_wide(const P4<T>* pts, const int32_t* gidx, const uint32_t* start, const GridGeom* G, int64_t M,
                      const P4<T>* rd, int64_t N, const Mat4<T>& Tm, int k, T maxR2, const T* radii, T* out_d,
@@ -205,24 +221,18 @@ void launch_knn_wide(const P4<T>* pts, const int32_t* gidx, const uint32_t* star
 
 
 // ---- grid match (pmx_grid.hip) ----
-// mode 0 = wave-cooperative LDS tiles, 1 = per-lane shell search (default).
-// ids written are positions in gpts;
-// launch_pos_to_index maps them back.  ctl / gd (device loop, modes 1-2):
-// transform and level are read on the device.  cold: a new reading's first
-// match (no previous match to certify from) on the tile kernel's cold form.
-// vout null: no counter-sum launch after the match (its counter phase is
-// merged into the select launch that follows, launch_select_all).
+// Launches what the plan says (pmx_match_plan.h).  D is the level the host
+// chose; ids written are positions in its gpts.  ctl / gd (device loop, every
+// form but the table's): the kernels take the transform, the level
+// (gd[ctl->level]) and the reuse mode from the device, and under tile
+// dispatch ctl->use_tile lets one of the two enqueued kernels run.
 void set_tile_prof(unsigned long long* buf);
 template <typename T>
-void launch_grid_match(int mode, const P4<T>* gpts, const int32_t* gidx, const uint32_t* start, const double* lo,
-                       double h, const int* g, const P4<T>* rd, int64_t N, const uint32_t* waves, int64_t n_waves,
-                       const Mat4<T>& Tm, int knn, T maxR2, uint32_t max_pts, T* dists, int32_t* ids,
-                       unsigned long long* vpart, unsigned long long* vout, int* iter_err, const GridReuse<T>& ru,
+void launch_grid_match(const GridMatchPlan& plan, const GridDesc<T>& D, const MatchQuery<T>& Q, const MatchOut<T>& O,
                        const LoopCtl* ctl, const GridDesc<T>* gd, SpecSel* spec, SelectState* spec_st,
-                       unsigned long long* xseg, const T* radii, bool cold, bool tile_disp, hipEvent_t ev_start,
-                       hipEvent_t ev_end, hipStream_t s);
+                       hipEvent_t ev_start, hipEvent_t ev_end, hipStream_t s);
 // several ranks: the quantile window's pick over the all-gathered segments
-// (pmx_spec.h); xseg above is this rank's segment, packed by the counter sum.
+// (pmx_spec.h); MatchOut::xseg is this rank's segment, packed by the counter sum.
 // stall: a miss sets ctl->done = kCtlStalled (the host did not read the
 // verdict; it replays the iteration).  force_miss: treat the window as
 // missed (test hook, option force_miss).

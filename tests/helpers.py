@@ -99,6 +99,41 @@ def dense_kit():
     return _dense_kit
 
 
+_match_plan = None
+
+
+def match_plan():
+    """Build tests/match_plan_shim.cpp the way dense_kit builds its shim and
+    return plan(facts) -> dict: plan_grid_match (csrc/pmx_match_plan.h) on a
+    dict of facts (missing ones: 0)."""
+    global _match_plan
+    if _match_plan is None:
+        cxx = shutil.which("g++")
+        if cxx is None:
+            raise FileNotFoundError("g++")
+        tmp = tempfile.mkdtemp(prefix="pmx_match_plan_shim_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        so = os.path.join(tmp, "libmatch_plan_shim.so")
+        subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC",
+                               "-I", os.path.join(ROOT, "libpointmatcher_amd", "csrc"),
+                               os.path.join(TESTS, "match_plan_shim.cpp"), "-o", so])
+        lib = ctypes.CDLL(so)
+        facts = ("grid_mode", "knn", "N", "reuse_on", "nbr_on", "safe_valid", "have_match", "ids_grid", "prev_knn",
+                 "same_level", "nbr_prev", "level_normals", "loop_on", "tile_dispatch", "window_on", "step_counters",
+                 "have_counters")
+        fields = ("form", "run", "reuse", "kt", "nbr", "nbr_normals", "window", "counter_sum", "safe_valid", "nbr_prev")
+
+        def plan(f):
+            assert set(f) <= set(facts), set(f) - set(facts)
+            a = (ctypes.c_longlong * len(facts))(*[int(f.get(k, 0)) for k in facts])
+            out = (ctypes.c_int * len(fields))()
+            lib.pmx_plan_grid_match(a, out)
+            return dict(zip(fields, out))
+
+        _match_plan = plan
+    return _match_plan
+
+
 def hom(a, dtype=None):
     a = np.asarray(a)
     dtype = dtype or a.dtype

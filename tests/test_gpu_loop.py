@@ -207,3 +207,65 @@ def test_quantile_window_is_exact(monkeypatch, dtype, filt, knn, max_dist):
     assert hits + misses == 30 and hits >= 15, (hits, misses)
     assert kept1 == kept0
     assert np.array_equal(tr1, tr0)
+
+
+# ---- tile dispatch (LoopCfg.tile_dispatch): the per-lane kernel and the tile
+# kernel's warm form enqueued back to back, LoopCtl.use_tile picks one ----
+TD_N, TD_M = 64 * 64 + 37, 1000  # (no multiple of 64 or 256; N >= 4 M: the automatic rule turns it on)
+_td_cache = {}
+
+
+def _td_scene(dtype):
+    ref, nrm = reference_cloud(TD_M, dtype)
+    return reading_cloud(TD_N, dtype), ref, nrm
+
+
+def _td_run(monkeypatch, dtype, knn, opts, mode):
+    monkeypatch.setenv("PMX_OPTS", opts)
+    monkeypatch.setenv("PMX_DEVICE_LOOP", "1" if mode == "loop" else "0")
+    rd, ref, nrm = _td_scene(dtype)
+    icp = ICP(dtype)
+    icp.load_yaml(chain_yaml(knn=knn, minimizer="PointToPlaneErrorMinimizer", maxit=25, differential=DIFF))
+    T = icp.compute(rd, ref, nrm)
+    st = icp.stats()
+    return T, st, icp.loop_diag(0, st.iterations) if mode == "loop" else None
+
+
+def _td_reference(monkeypatch, oracle, dtype, knn):
+    """The per-module path and the oracle, once per (dtype, knn)."""
+    key = (np.dtype(dtype).name, knn)
+    if key not in _td_cache:
+        Tm, sm, _ = _td_run(monkeypatch, dtype, knn, "", "modules")
+        rd, ref, nrm = _td_scene(dtype)
+        cfg = oracle.make_cfg(knn=knn, minimizer="PointToPlaneErrorMinimizer", counter_max=25, differential=DIFF,
+                              threads=8)
+        rc, To, so, _ = oracle.icp(cfg, rd, ref, normals=nrm, trace=False)
+        assert rc == 0
+        _td_cache[key] = (Tm, sm, To, so.iterations)
+    return _td_cache[key]
+
+
+@pytest.mark.parametrize("knn", [1, 3])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_tile_dispatch_equals_modules(monkeypatch, oracle, dtype, knn):
+    """A reading much denser than the reference: the loop with tile dispatch
+    off, on and chosen by the automatic rule (N >= 4 x the reference) against
+    the per-module path and the oracle.  Every form of the match is exact, so
+    the bar is test_loop_equals_modules'.  Not vacuous: the diagnostic record's
+    full-search count of iteration 0 (the cold match counts every query) is
+    what the step's rule reads (>= 85 % of the queries: the warm tile form runs
+    iteration 1), and iteration 1's pair count then differs from the per-lane
+    kernel's, because the tile forms report a shell-search estimate."""
+    Tm, sm, To, oracle_iters = _td_reference(monkeypatch, oracle, dtype, knn)
+    diag = {}
+    for name, opts in (("off", "tile_dispatch=0"), ("on", "tile_dispatch=1"), ("auto", "")):
+        Tl, sl, diag[name] = _td_run(monkeypatch, dtype, knn, opts, "loop")
+        assert sl.iterations == sm.iterations == oracle_iters, name
+        assert np.linalg.norm(Tl - Tm) <= TOL[dtype], name
+        assert np.linalg.norm(Tl - To) <= TOL[dtype], name
+        assert sl.kept == sm.kept, name
+        assert sl.rejected_matches == sm.rejected_matches, name
+    assert sm.iterations >= 2
+    for name in ("on", "auto"):
+        assert diag[name][0, 3] >= 0.85 * TD_N, name      # the step chose the warm tile form for iteration 1
+        assert diag[name][1, 2] != diag["off"][1, 2], name  # ... and it ran: not the per-lane kernel's pair count
