@@ -39,6 +39,11 @@
  *                         estimateCovariance (ErrorMinimizers/
  *                         PointToPlaneWithCov.cpp:72-162), read through
  *                         ErrorMinimizer::getCovariance (PointMatcher.h:553)
+ *   pmx_match_quality / pmx_loop_quality
+ *                       the sums of ErrorMinimizer::getResidualError and
+ *                         getOverlap (PointMatcher.h:552-554; PointToPlane.cpp:
+ *                         316-465, PointToPoint.cpp:104-164), with
+ *                         pmx_set_reading_noise / pmx_set_reference_descriptors
  *   pmx_get_matches /   lazy host mirrors of Matches / OutlierWeights for
  *   pmx_get_weights       CPU modules and inspectors (PointMatcher.h:371-391)
  *
@@ -195,6 +200,17 @@ int pmx_set_reading_radii(pmx_ctx* ctx, const void* radii);
  * in T, and the records follow the reading's slot order.  Cleared by the next
  * pmx_set_reading. */
 int pmx_set_reading_normals(pmx_ctx* ctx, const void* normals);
+/* ErrorMinimizer::getOverlap's descriptors (pmx_match_quality).  The reading's
+ * "simpleSensorNoise": N T values in the order of pmx_set_reading's points (a
+ * sharded context takes its shard's), kept in the reading's slot order; NULL
+ * clears, and so does the next pmx_set_reading. */
+int pmx_set_reading_noise(pmx_ctx* ctx, const void* noise);
+/* The reference's "simpleSensorNoise" and "densities": M T values each, in the
+ * order of pmx_set_reference's points; either may be NULL (absent).  Every call
+ * replaces both; the next pmx_set_reference clears them.  The densities must
+ * not be NaN: the median is taken from their sorted order, where a NaN would
+ * rank by its bit pattern. */
+int pmx_set_reference_descriptors(pmx_ctx* ctx, const void* noise, const void* densities);
 
 /* ------------------------------------------------------------- match --- */
 /* search structure, mirroring KDTreeMatcher's searchType
@@ -293,6 +309,54 @@ int pmx_p2point_similarity_system(pmx_ctx* ctx, double* mean_p, double* mean_q, 
  * PMX_E_BAD_PARAM for a 2-D context or a reference without normals (the
  * reference returns max * I there, :91-92); PMX_E_STATE without a match. */
 int pmx_p2plane_covariance(pmx_ctx* ctx, const void* T_step, double* H, double* Q, int64_t* pairs);
+/* ErrorMinimizer::getResidualError and getOverlap (PointMatcher.h:552-554) for
+ * the last pmx_match and its recorded filter chain, as reductions over the
+ * resident match.  minimizer: 0 PointToPlane, 1 PointToPoint, 2
+ * PointToPlaneWithCov, 3 PointToPointSimilarity (pmx_loop_cfg's numbers).
+ * T_step (rows x rows row-major T; NULL: the match's own T_iter) transforms the
+ * reading for the point-to-plane residual.  Over the ErrorElements columns
+ * (the kept links: dist != inf && w != 0, w the chain's weight as
+ * pmx_get_weights returns it), every term in T in the reference's order, the
+ * sums in double:
+ *   residual   point-to-plane: sum w ((d . n)^2), d = T_step p - q
+ *              (PointToPlane.cpp:338-350); point-to-point and similarity: sum
+ *              sqrt(dist), the match's own squared distance (PointToPoint.cpp:
+ *              155-164)
+ *   links      the number of columns;  dist_sum: sum sqrt(dist)
+ *   overlap    num / den by the branch the descriptors present select
+ *              (pmx_set_reading_noise, pmx_set_reference_descriptors):
+ *     point-to-plane (PointToPlane.cpp:387-464): a link's uncertainty u in T is
+ *       branch 1  (medianRadius + noise_rd[i]) + noise_ref[id]  (both noises
+ *                 and densities; medianRadius = 1 / pow(medianDensity, 1/3.) in
+ *                 double, medianDensity the element (size_t)(links * 0.5) of
+ *                 the kept links' reference densities in ascending order)
+ *       branch 2  noise_rd[i] + noise_ref[id];  3  noise_rd[i];  4  noise_ref[id]
+ *       num = reading points with a kept link of sqrt(dist) < u, den = reading
+ *       points with a kept link + nbRejectedPoints.
+ *     point-to-point (PointToPoint.cpp:139-151), branch 3 (reading noise):
+ *       mean = (T)(dist_sum / links); num = links with sqrt(dist) < mean +
+ *       noise_rd[i], den = links.
+ *     branch 0: no noise present, num = den = 0 and the caller falls back to
+ *       the weighted used ratio (getWeightedPointUsedRatio).
+ * The reference identifies a reading point by comparing the coordinates of
+ * consecutive ErrorElements columns (PointToPlane.cpp:435-459), so two reading
+ * points with identical transformed coordinates that are adjacent among the
+ * kept links count as one there; here every reading point counts for itself.
+ * The two agree whenever no two reading points coincide.
+ * Without a kept link num = den = 0 and no second pass runs.
+ * Global over all ranks: one all-reduce per pass (two with an overlap branch).
+ * Branch 1 over more than one rank returns PMX_E_BAD_PARAM (the median of the
+ * ranks' densities is not implemented).  Synchronises the stream; PMX_E_STATE
+ * without a match. */
+typedef struct pmx_quality {
+    double residual;
+    int64_t overlap_num, overlap_den;
+    int64_t links;
+    double dist_sum;
+    double median_density; /* branch 1 only, a T value */
+    int branch;
+} pmx_quality;
+int pmx_match_quality(pmx_ctx* ctx, const void* T_step, int minimizer, pmx_quality* out);
 
 /* ---------------------------------------------------------- host mirrors --- */
 /* dists: k x N T (point-major), ids: k x N int32 (this rank's shard) */
@@ -396,6 +460,11 @@ int pmx_loop_run(pmx_ctx* ctx, int n, pmx_loop_status* st);
  * loop is not done, after a loop that stopped on an error, or one begun with
  * another minimizer; PMX_E_BAD_PARAM for a 2-D context. */
 int pmx_loop_covariance(pmx_ctx* ctx, double* H, double* Q, int64_t* pairs);
+/* pmx_match_quality for a finished loop, whatever its minimizer: the last
+ * executed iteration's match, limits and step transform are still on the
+ * device.  PMX_E_STATE before a loop has finished or after one that stopped on
+ * an error. */
+int pmx_loop_quality(pmx_ctx* ctx, int minimizer, pmx_quality* out);
 /* T_iter after each completed iteration (keep_trace): count x rows x rows T */
 int pmx_loop_trace(pmx_ctx* ctx, int first, int count, void* out);
 /* Quantile window statistics of the device loop (no reference counterpart;

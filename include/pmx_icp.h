@@ -106,6 +106,32 @@ int pmx_icp_stats_get(const pmx_icp* icp, pmx_icp_stats* out);
  * 2-D ICP, :91-92), computed once when the loop stops; zeros for every other
  * minimiser. */
 int pmx_icp_covariance(pmx_icp* icp, void* cov36);
+/* errorMinimizer->getOverlap() and getResidualError() (PointMatcher.h:552-554)
+ * for the last iteration of the last compute.  The chain keeps the filtered
+ * clouds' "simpleSensorNoise" (reading and reference, or the ICPSequence map)
+ * and the reference's "densities" when present (from a data filter such as
+ * SimpleSensorNoiseDataPointsFilter / SurfaceNormalDataPointsFilter, or
+ * pmx_icp_add_descriptor); on the first call after the loop stopped they are
+ * uploaded and the sums taken on the device from the match still resident
+ * there (pmx_match_quality / pmx_loop_quality, include/pmx.h: the branches and
+ * the one difference from the reference's scan), then cached until the next
+ * prepare / set_map.  An ICP that never calls them launches nothing for them.
+ * Without any noise descriptor the overlap is the weighted used ratio
+ * (pmx_icp_stats.overlap_ratio, which always stays that ratio, ICP.cpp:435).
+ * PointToPlane (and WithCov), PointToPoint and PointToPointSimilarity; any
+ * other minimiser returns the base class's weighted used ratio and max().
+ * Before a compute has stopped: PMX_ICP_RUNTIME_ERROR with the reference's
+ * text (PointToPlane.cpp:384).  A multi-rank ICP calls them on every rank. */
+int pmx_icp_overlap(pmx_icp* icp, double* overlap);
+int pmx_icp_residual_error(pmx_icp* icp, double* residual);
+/* Inspection: the descriptor `name` of a cloud (rows x n, T) after the chain's
+ * readingDataPointsFilters (cloud 0) or referenceDataPointsFilters (cloud 1),
+ * with the descriptors staged for that cloud.  *n_out the filtered point count,
+ * *span the descriptor's rows (0: absent); out (may be NULL to size) receives
+ * n_out * span point-major T values, capacity in values.  Filters that run on
+ * the GPU need one. */
+int pmx_icp_filtered_descriptor(pmx_icp* icp, int cloud, const void* feat, int rows, int64_t n, const char* name,
+                                void* out, int64_t capacity, int64_t* n_out, int* span);
 /* T_iter after each iteration (rows x rows each), returns count written */
 int pmx_icp_trace_get(const pmx_icp* icp, void* out, int max_iters);
 /* HIP-event device time of the match kernel over the last iterations */

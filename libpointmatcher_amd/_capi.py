@@ -146,6 +146,15 @@ def gloo_host_comm():
     return HostComm(dist.get_world_size(), dist.get_rank(), allreduce, allgather)
 
 
+class Quality(C.Structure):
+    """pmx_quality (include/pmx.h): getResidualError / getOverlap's sums."""
+    _fields_ = [("residual", C.c_double), ("overlap_num", C.c_int64), ("overlap_den", C.c_int64),
+                ("links", C.c_int64), ("dist_sum", C.c_double), ("median_density", C.c_double), ("branch", C.c_int)]
+
+
+MINIMIZER_KIND = {"PointToPlaneErrorMinimizer": 0, "PointToPointErrorMinimizer": 1,
+                  "PointToPlaneWithCovErrorMinimizer": 2, "PointToPointSimilarityErrorMinimizer": 3}
+
 _lib = None
 
 EXPORTS = [
@@ -154,7 +163,7 @@ EXPORTS = [
     "pmx_outlier_default", "pmx_outlier_null", "pmx_outlier_maxdist", "pmx_outlier_mindist",
     "pmx_outlier_mediandist", "pmx_outlier_trimmed", "pmx_outlier_vartrimmed", "pmx_outlier_robust",
     "pmx_robust_scale", "pmx_set_reading_radii", "pmx_set_reading_normals", "pmx_outlier_surface_normal",
-    "pmx_p2plane_system", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
+    "pmx_p2plane_system", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid",
@@ -205,6 +214,10 @@ def lib():
                                                     C.POINTER(C.c_double), C.POINTER(Stats)]
         l.pmx_p2plane_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         l.pmx_loop_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        l.pmx_set_reading_noise.argtypes = [C.c_void_p, C.c_void_p]
+        l.pmx_set_reference_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pmx_match_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Quality)]
+        l.pmx_loop_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(Quality)]
         l.pmx_get_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         l.pmx_get_weights.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_vartrim_partial_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
@@ -560,6 +573,36 @@ class Context:
         n = C.c_int64(0)
         self._chk(self._l.pmx_loop_covariance(self.h, _ptr(H), _ptr(Q), C.byref(n)))
         return H, Q, n.value
+
+    def set_reading_noise(self, noise):
+        """The reading's simpleSensorNoise, N values in set_reading's order (None clears)."""
+        n = self._arr(noise).ravel() if noise is not None else None
+        if n is not None and n.size != self.N:
+            raise InvalidParameter(f"reading noise must have {self.N} values, not {n.size}")
+        self._chk(self._l.pmx_set_reading_noise(self.h, _ptr(n)))
+
+    def set_reference_descriptors(self, noise=None, densities=None):
+        """The reference's simpleSensorNoise and densities, M values each in
+        set_reference's order (None: absent)."""
+        M = self._ref_keep[0].shape[0]
+        arrs = [self._arr(a).ravel() if a is not None else None for a in (noise, densities)]
+        for a in arrs:
+            if a is not None and a.size != M:
+                raise InvalidParameter(f"reference descriptors must have {M} values, not {a.size}")
+        self._chk(self._l.pmx_set_reference_descriptors(self.h, _ptr(arrs[0]), _ptr(arrs[1])))
+
+    def match_quality(self, minimizer="PointToPlaneErrorMinimizer", T_step=None):
+        """getResidualError / getOverlap's sums for the last match (pmx_match_quality)."""
+        q = Quality()
+        T = self._arr(T_step) if T_step is not None else None
+        self._chk(self._l.pmx_match_quality(self.h, _ptr(T), MINIMIZER_KIND[minimizer], C.byref(q)))
+        return q
+
+    def loop_quality(self, minimizer="PointToPlaneErrorMinimizer"):
+        """The same for the last iteration of a finished device loop (pmx_loop_quality)."""
+        q = Quality()
+        self._chk(self._l.pmx_loop_quality(self.h, MINIMIZER_KIND[minimizer], C.byref(q)))
+        return q
 
     def get_matches(self):
         d = np.empty((self.N, self.knn), self.dtype)

@@ -165,6 +165,35 @@ void covariance_impl(pmx_icp* icp, void* cov36) {
 }
 
 template <typename T>
+double quality_impl(pmx_icp* icp, bool overlap) {
+    auto& I = get<T>(icp);
+    if (!I.errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
+    return overlap ? (double)I.errorMinimizer->getOverlap() : (double)I.errorMinimizer->getResidualError();
+}
+
+// one chain of data filters applied to a copy of the caller's cloud
+template <typename T>
+void filtered_descriptor_impl(pmx_icp* icp, int cloud, const void* feat, int rows, int64_t n, const char* name,
+                              void* out, int64_t capacity, int64_t* n_out, int* span_out) {
+    auto& I = get<T>(icp);
+    auto borrowed = make_cloud<T>(feat, rows, n, nullptr);
+    take_staged<T>(icp, cloud, borrowed);
+    DataPoints<T> c(borrowed);
+    auto& chain = cloud == 0 ? I.readingDataPointsFilters : I.referenceDataPointsFilters;
+    chain.init();
+    chain.apply(c);
+    int span = 0;
+    std::vector<T> v;
+    if (c.descriptorExists(name)) v = c.descriptor(name, &span);
+    if (n_out) *n_out = c.n;
+    if (span_out) *span_out = span;
+    if (!out) return;
+    if (capacity < 0 || (uint64_t)capacity < (uint64_t)v.size())
+        throw InvalidParameter("pmx_icp_filtered_descriptor: capacity below n * span");
+    std::memcpy(out, v.data(), sizeof(T) * v.size());
+}
+
+template <typename T>
 void stats_impl(const pmx_icp* icp, pmx_icp_stats* s) {
     auto& I = get<T>(const_cast<pmx_icp*>(icp));
     std::memset(s, 0, sizeof(*s));
@@ -372,6 +401,28 @@ int pmx_icp_stats_get(const pmx_icp* icp, pmx_icp_stats* out) {
 int pmx_icp_covariance(pmx_icp* icp, void* cov36) {
     if (!icp || !cov36) return PMX_ICP_INVALID_PARAMETER;
     return guarded(icp, [&] { BOTH(icp, covariance_impl<float>(icp, cov36), covariance_impl<double>(icp, cov36)); });
+}
+
+int pmx_icp_overlap(pmx_icp* icp, double* overlap) {
+    if (!icp || !overlap) return PMX_ICP_INVALID_PARAMETER;
+    return guarded(icp, [&] { *overlap = BOTH(icp, quality_impl<float>(icp, true), quality_impl<double>(icp, true)); });
+}
+
+int pmx_icp_residual_error(pmx_icp* icp, double* residual) {
+    if (!icp || !residual) return PMX_ICP_INVALID_PARAMETER;
+    return guarded(icp,
+                   [&] { *residual = BOTH(icp, quality_impl<float>(icp, false), quality_impl<double>(icp, false)); });
+}
+
+int pmx_icp_filtered_descriptor(pmx_icp* icp, int cloud, const void* feat, int rows, int64_t n, const char* name,
+                                void* out, int64_t capacity, int64_t* n_out, int* span) {
+    if (!icp) return PMX_ICP_INVALID_PARAMETER;
+    return guarded(icp, [&] {
+        if (!name || (!feat && n > 0) || n < 0 || (rows != 3 && rows != 4) || (cloud != 0 && cloud != 1))
+            throw InvalidParameter("pmx_icp_filtered_descriptor: bad arguments");
+        BOTH(icp, filtered_descriptor_impl<float>(icp, cloud, feat, rows, n, name, out, capacity, n_out, span),
+             filtered_descriptor_impl<double>(icp, cloud, feat, rows, n, name, out, capacity, n_out, span));
+    });
 }
 
 int pmx_icp_trace_get(const pmx_icp* icp, void* out, int max_iters) {

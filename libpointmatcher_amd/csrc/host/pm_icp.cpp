@@ -493,6 +493,7 @@ struct PointToPlaneEM : PM<T>::ErrorMinimizer {
         build_p2plane_transform(rows, x, out);
         return out;
     }
+    int qualityKind() const override { return 0; }
     bool loopConfig(pmx_loop_cfg& cfg) const override {
         cfg.minimizer = 0;
         return !force2D && !force4DOF;
@@ -519,6 +520,7 @@ struct PointToPlaneWithCovEM : PointToPlaneEM<T> {
         : PointToPlaneEM<T>("PointToPlaneWithCovErrorMinimizer", doc(), p),
           sensorStdDev(this->template get<T>("sensorStdDev")),
           covMatrix(36, (T)0) {}
+    int qualityKind() const override { return 2; }
     bool loopConfig(pmx_loop_cfg& cfg) const override {
         cfg.minimizer = 2;  // (PointToPlane's iterations; the step keeps the increments)
         return !this->force2D && !this->force4DOF;
@@ -566,6 +568,7 @@ struct PointToPointEM : PM<T>::ErrorMinimizer {
         dense::p2point_transform(rows, m, mpT, mqT, out.data());  // (shared with the device loop)
         return out;
     }
+    int qualityKind() const override { return 1; }
     bool loopConfig(pmx_loop_cfg& cfg) const override {
         cfg.minimizer = 1;
         return true;
@@ -598,6 +601,7 @@ struct PointToPointSimilarityEM : PM<T>::ErrorMinimizer {
         dense::p2point_similarity_transform(rows, m, mpT, mqT, (T)sigma, out.data());  // (shared with the device loop)
         return out;
     }
+    int qualityKind() const override { return 3; }
     bool loopConfig(pmx_loop_cfg& cfg) const override {
         cfg.minimizer = 3;
         return true;
@@ -921,6 +925,60 @@ struct DistDPF : PM<T>::DataPointsFilter {
             }
             return kMax ? (f[dim] < limit) : (f[dim] > limit);
         });
+    }
+};
+
+// SimpleSensorNoiseDataPointsFilter (DataPointsFilters/SimpleSensorNoise.cpp:
+// 44-136, parameters SimpleSensorNoise.h:62-63): the descriptor
+// "simpleSensorNoise" (span 1) from each point's Euclidean norm, by one of five
+// sensor models: max(minRadius, beamAngle * norm + beamConst) for the four
+// lasers, norm^2 * (0.5 * 0.00285) for Kinect / Xtion, every operation in T.
+// gain is read and unused, as in the reference.  Host code, elementwise, once
+// per compute, like the MaxDist filter above.
+template <typename T>
+struct SimpleSensorNoiseDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("sensorType",
+                     "Type of the sensor used. Choices: 0=Sick LMS-1xx, 1=Hokuyo URG-04LX, 2=Hokuyo UTM-30LX, "
+                     "3=Kinect/Xtion",
+                     "0", "0", "2147483647", &P::Comp<unsigned>),
+                PDoc("gain",
+                     "If the point cloud is coming from an untrusty source, you can use the gain to augment the "
+                     "uncertainty",
+                     "1", "1", "inf", &P::Comp<T>)};
+    }
+    const unsigned sensorType;
+    const T gain;
+    explicit SimpleSensorNoiseDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("SimpleSensorNoiseDataPointsFilter", doc(), p),
+          sensorType(this->template get<unsigned>("sensorType")),
+          gain(this->template get<T>("gain")) {
+        if (sensorType >= 5)  // (the five sensor names, SimpleSensorNoise.cpp:53-61)
+            throw InvalidParameter("SimpleSensorNoiseDataPointsFilter: Error, sensorType id " +
+                                   std::to_string(sensorType) + " does not exist.");
+    }
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        // {minRadius, beamAngle, beamConst} of computeLaserNoise, :87-113
+        static const double laser[5][3] = {{0.012, 0.0068, 0.0008}, {0.028, 0.0013, 0.0001}, {0.018, 0.0006, 0.0015},
+                                           {0, 0, 0}, {0.004, 0.0053, -0.0092}};
+        const int dim = cloud.rows, D = dim - 1;
+        std::vector<T> noise((size_t)cloud.n);
+        const T minRadius = (T)laser[sensorType][0], beamAngle = (T)laser[sensorType][1],
+                beamConst = (T)laser[sensorType][2];
+        for (int64_t j = 0; j < cloud.n; ++j) {
+            const T* f = &cloud.features[(size_t)j * dim];
+            T s = f[0] * f[0];
+            for (int r = 1; r < D; ++r) s = s + f[r] * f[r];
+            const T norm = std::sqrt(s);
+            if (sensorType == 3) {
+                noise[(size_t)j] = (norm * norm) * (T)(0.5 * 0.00285);  // :105-106
+            } else {
+                const T v = beamAngle * norm + beamConst;  // :131-135
+                noise[(size_t)j] = v > minRadius ? v : minRadius;
+            }
+        }
+        cloud.setDescriptor("simpleSensorNoise", 1, noise.data());
     }
 };
 
@@ -1299,6 +1357,8 @@ PointMatcher<T>::PointMatcher() {
                                   [](const Ps& p) { return std::make_shared<DistDPF<T, true>>(p); }, true);
     DataPointsFilterRegistrar.reg("MinDistDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<DistDPF<T, false>>(p); }, true);
+    DataPointsFilterRegistrar.reg("SimpleSensorNoiseDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<SimpleSensorNoiseDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("DistanceLimitDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<DistanceLimitDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("VoxelGridDataPointsFilter",
@@ -1494,6 +1554,7 @@ void PointMatcher<T>::ICP::prepare(const DataPoints& readingIn, const DataPoints
     dev.ensure();
     mapIndexed_ = false;  // (an ICPSequence map is no longer the device's reference, even if init throws)
     matcher->init(dev, reference, nullptr, mean);  // ICP.cpp:302 (features - mean, ICP.cpp:299, on the device)
+    keepReferenceDescriptors(reference);
     for (int r = 0; r < dim - 1; ++r) T_refIn_refMean_[r * dim + dim - 1] = mean[r];
     referencePreprocessingDuration = since<T>(t);
     prefilteredReferencePtsCount = M;
@@ -1534,6 +1595,8 @@ void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const Tra
     dev.check(pmx_set_reading(dev.ctx, reading.feat(), dim, reading.n, T_refMean_dataIn_.data()));
     matcher->initReading(dev, reading);  // (per-reading matcher inputs: KDTreeVarDistMatcher's radii)
     uploadReadingNormals(reading);       // (SurfaceNormalOutlierFilter; rotated by T_refMean_dataIn on the device)
+    keepReadingNoise(reading);
+    errorMinimizer->quality_.stopped = errorMinimizer->quality_.valid = false;  // (a new compute: the cache goes)
     // readingStepDataPointsFilters (ICP.cpp:349-350, 373-377): the step
     // filters see the reading in <refMean> every iteration; keep that copy on
     // the host (the device's transform, restated: the same separately rounded
@@ -1633,6 +1696,8 @@ bool PointMatcher<T>::ICP::setMap(const DataPoints& inputCloud) {
     if (map.n <= 0) throw ConvergenceError("empty reference");
     dev.ensure();
     matcher->init(dev, map);  // ICP.cpp:503 (the grid stays on the device)
+    keepReferenceDescriptors(map);
+    if (errorMinimizer) errorMinimizer->quality_.stopped = errorMinimizer->quality_.valid = false;
     map_ = std::move(map);
     T_map_ = std::move(T_map);
     mapIndexed_ = true;
@@ -1666,6 +1731,7 @@ void PointMatcher<T>::ICP::reinitMap() {
     if (!hasMap() || !matcher) return;
     dev.ensure();
     matcher->init(dev, map_);
+    keepReferenceDescriptors(map_);
     mapIndexed_ = true;
 }
 
@@ -1722,6 +1788,75 @@ void PointMatcher<T>::ICP::uploadReadingNormals(const DataPoints& reading) {
         throw InvalidElement("SurfaceNormalOutlierFilter: descriptor normals must have " +
                              std::to_string(reading.rows - 1) + " rows, not " + std::to_string(span));
     dev.check(pmx_set_reading_normals(dev.ctx, nr.data()));
+}
+
+template <typename T>
+void PointMatcher<T>::ICP::keepReadingNoise(const DataPoints& reading) {
+    rdNoise_.clear();
+    if (!reading.descriptorExists("simpleSensorNoise")) return;
+    int span = 0;
+    std::vector<T> v = reading.descriptor("simpleSensorNoise", &span);
+    if (span != 1) throw InvalidElement("descriptor simpleSensorNoise must have 1 row, not " + std::to_string(span));
+    rdNoise_ = std::move(v);
+}
+
+template <typename T>
+void PointMatcher<T>::ICP::keepReferenceDescriptors(const DataPoints& reference) {
+    refNoise_.reset();
+    refDens_.reset();
+    for (const char* name : {"simpleSensorNoise", "densities"}) {
+        if (!reference.descriptorExists(name)) continue;
+        int span = 0;
+        std::vector<T> v = reference.descriptor(name, &span);
+        if (span != 1)
+            throw InvalidElement(std::string("descriptor ") + name + " must have 1 row, not " + std::to_string(span));
+        (name[0] == 's' ? refNoise_ : refDens_) = std::make_shared<const std::vector<T>>(std::move(v));
+    }
+}
+
+// a checker stopped the loop: the last match stays resident until the next
+// prepare / setMap, and the minimiser may be asked about it
+template <typename T>
+void PointMatcher<T>::ICP::stopped(bool deviceLoop) {
+    auto& q = errorMinimizer->quality_;
+    q.dev = &dev;
+    q.stopped = true;
+    q.loop = deviceLoop;
+    q.valid = false;
+    q.readingNoise = rdNoise_;
+    q.refNoise = refNoise_;
+    q.refDens = refDens_;
+}
+
+template <typename T>
+const pmx_quality& PointMatcher<T>::ErrorMinimizer::quality() const {
+    Quality& s = quality_;
+    if (!s.stopped || !s.dev)  // PointToPlane.cpp:382-385, PointToPoint.cpp:126-129
+        throw std::runtime_error("Error, last error element empty. Error minimizer needs to be called at least once "
+                                 "before using this method.");
+    if (s.valid) return s.q;
+    const Device& d = *s.dev;
+    d.check(pmx_set_reading_noise(d.ctx, s.readingNoise.empty() ? nullptr : s.readingNoise.data()));
+    d.check(pmx_set_reference_descriptors(d.ctx, s.refNoise ? s.refNoise->data() : nullptr,
+                                          s.refDens ? s.refDens->data() : nullptr));
+    d.check(s.loop ? pmx_loop_quality(d.ctx, qualityKind(), &s.q)
+                   : pmx_match_quality(d.ctx, nullptr, qualityKind(), &s.q));
+    s.valid = true;
+    return s.q;
+}
+
+template <typename T>
+T PointMatcher<T>::ErrorMinimizer::getOverlap() const {
+    if (qualityKind() < 0) return weightedPointUsedRatio;
+    const pmx_quality& q = quality();
+    if (q.branch == 0) return weightedPointUsedRatio;  // (no sensor noise: the reference's fallback)
+    return (T)q.overlap_num / (T)q.overlap_den;        // PointToPlane.cpp:464, PointToPoint.cpp:151
+}
+
+template <typename T>
+T PointMatcher<T>::ErrorMinimizer::getResidualError() const {
+    if (qualityKind() < 0) return std::numeric_limits<T>::max();  // ErrorMinimizer.cpp:274-278
+    return (T)quality().residual;
 }
 
 // every module's device form, or false (ICP.cpp:371-430 then runs through the
@@ -1790,7 +1925,10 @@ bool PointMatcher<T>::ICP::iterate(int n) {
     if (rc != PMX_OK) dev.check(rc);  // the exception the loop raised
     // (stopped by a checker: the last iteration's match is still resident,
     // nothing has replaced it yet)
-    if (st.done && fresh > 0) errorMinimizer->loopStopped(dev, dim, nullptr);
+    if (st.done && fresh > 0) {
+        errorMinimizer->loopStopped(dev, dim, nullptr);
+        stopped(true);
+    }
     return iterate_;
 }
 
@@ -1810,6 +1948,7 @@ bool PointMatcher<T>::ICP::stepModules() {
         dev.check(pmx_set_reading(dev.ctx, stepReading.features.data(), dim, stepReading.n, I.data()));
         matcher->initReading(dev, stepReading);
         uploadReadingNormals(stepReading);
+        keepReadingNoise(stepReading);  // (the last iteration's is the one getOverlap reads)
     }
     const Matches matches = matcher->findClosests(dev, T_iter_);
     outlierFilters.compute(dev, matches);
@@ -1825,7 +1964,10 @@ bool PointMatcher<T>::ICP::stepModules() {
     ++iterationCount;
     if (keepTrace) trace.push_back(T_iter_);
     // (the loop has stopped: this iteration's match is still resident)
-    if (!iterate_) errorMinimizer->loopStopped(dev, dim, dT.data());
+    if (!iterate_) {
+        errorMinimizer->loopStopped(dev, dim, dT.data());
+        stopped(false);
+    }
     return iterate_;
 }
 

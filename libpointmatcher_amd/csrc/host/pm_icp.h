@@ -134,7 +134,27 @@ struct PointMatcher {
         virtual void loopStopped(Device&, int /*rows*/, const T* /*dT*/) {}
         T getPointUsedRatio() const { return pointUsedRatio; }
         T getWeightedPointUsedRatio() const { return weightedPointUsedRatio; }
-        virtual T getOverlap() const { return weightedPointUsedRatio; }
+        // getOverlap / getResidualError (PointMatcher.h:552-554).  The base class
+        // (qualityKind() < 0: Identity, any plugin that does not override) returns
+        // the weighted used ratio and max(), ErrorMinimizer.cpp:274-278.  The four
+        // minimisers name their pmx_match_quality number; the sums are then taken
+        // from the last match, still resident on the device, on the first call
+        // after the ICP stopped, and cached until the next prepare / setMap.
+        virtual int qualityKind() const { return -1; }
+        virtual T getOverlap() const;
+        virtual T getResidualError() const;
+        // What the ICP leaves when a checker stops the loop: the device, which
+        // path ran (device loop or module calls), and host copies of the
+        // descriptors getOverlap reads (uploaded only when it is asked).
+        struct Quality {
+            Device* dev = nullptr;
+            bool stopped = false, loop = false, valid = false;
+            std::vector<T> readingNoise;
+            std::shared_ptr<const std::vector<T>> refNoise, refDens;
+            pmx_quality q{};
+        };
+        mutable Quality quality_;
+        const pmx_quality& quality() const;  // throws the reference's runtime_error before any compute
         void setStats(const pmx_stats& st);
     };
 
@@ -270,6 +290,15 @@ struct PointMatcher {
         // the reading's "normals" to the device when a filter of the chain
         // reads them (after every reading upload)
         void uploadReadingNormals(const DataPoints& reading);
+        // getOverlap's descriptors (ErrorMinimizer::Quality): host copies of the
+        // filtered clouds' "simpleSensorNoise" / "densities", handed to the
+        // minimiser when the loop stops (stopped); nothing is uploaded or
+        // launched unless getOverlap / getResidualError is called
+        void keepReadingNoise(const DataPoints& reading);
+        void keepReferenceDescriptors(const DataPoints& reference);
+        void stopped(bool deviceLoop);
+        std::vector<T> rdNoise_;
+        std::shared_ptr<const std::vector<T>> refNoise_, refDens_;
         DataPoints stepBase_;                 // the reading in <refMean> (readingStepDataPointsFilters)
         DataPoints map_;                      // the map in <refMean>, filtered (mapPointCloud)
         TransformationParameters T_map_;      // its T_refIn_refMean

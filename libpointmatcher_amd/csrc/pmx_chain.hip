@@ -510,6 +510,7 @@ int set_reference_impl(pmx_ctx* c, const T* feat, int rows, int64_t M, const T* 
     // packs them and sizes the grid; they are packed just before the level
     // builds, which interleave them (before_levels).
     c->has_normals = normals != nullptr;
+    c->has_ref_noise = c->has_ref_dens = false;  // (a new reference: its descriptors, if any, follow)
     std::thread nrm_thread;
     int nrm_rc = PMX_OK;
     const size_t nrm_bytes = sizeof(T) * (size_t)D * M;
@@ -572,6 +573,7 @@ int set_reading_impl(pmx_ctx* c, const T* feat, int rows, int64_t N, const T* T0
     SetupTrace tr(c);
     c->has_radii = false;  // (a new reading: its radii, if any, follow)
     c->has_rnrm = false;   // (and its normals, pmx_set_reading_normals)
+    c->has_rnoise = false; // (and its sensor noise, pmx_set_reading_noise)
     for (int i = 0; i < 16; ++i) c->T0[i] = (double)M0.m[i];
     // raw P4 reading (pack), then the slot order, then T_refMean_dataIn
     // (scratch and the resident reading kept across readings: ICPSequence
@@ -1345,6 +1347,47 @@ int set_reading_normals_impl(pmx_ctx* c, const T* normals) {
     return PMX_OK;
 }
 
+// getOverlap's descriptors (pmx_quality.h).  The reading's simpleSensorNoise
+// in slot order, exactly as the radii above.
+template <typename T>
+int set_reading_noise_impl(pmx_ctx* c, const T* noise) {
+    if (!noise) {
+        c->has_rnoise = false;
+        return PMX_OK;
+    }
+    if (!c->d_rd && c->N > 0) return fail(c, PMX_E_STATE, "pmx_set_reading must be called first");
+    const int64_t n1 = std::max<int64_t>(c->N, 1);
+    int rc;
+    if ((rc = ensure(c, &c->d_rnoise, &c->rnoise_bytes, 2 * sizeof(T) * (size_t)n1))) return rc;
+    T* raw = (T*)c->d_rnoise + n1;  // (upload half, then the slot-order half)
+    HIPCHK(c, hipMemcpyAsync(raw, noise, sizeof(T) * (size_t)c->N, hipMemcpyHostToDevice, c->stream));
+    launch_gather_scalar<T>(raw, c->has_order ? c->d_order : nullptr, c->N, (T*)c->d_rnoise, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's buffer may go)
+    c->has_rnoise = true;
+    return PMX_OK;
+}
+// the reference's simpleSensorNoise and densities, M values each in original id order
+template <typename T>
+int set_reference_descriptors_impl(pmx_ctx* c, const T* noise, const T* dens) {
+    if (!c->d_ref) return fail(c, PMX_E_STATE, "pmx_set_reference must be called first");
+    const size_t bytes = sizeof(T) * (size_t)c->M;
+    int rc;
+    c->has_ref_noise = c->has_ref_dens = false;
+    if (noise) {
+        if ((rc = ensure(c, &c->d_ref_noise, &c->ref_noise_bytes, bytes))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_ref_noise, noise, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    if (dens) {
+        if ((rc = ensure(c, &c->d_ref_dens, &c->ref_dens_bytes, bytes))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_ref_dens, dens, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's buffers may go)
+    c->has_ref_noise = noise != nullptr;
+    c->has_ref_dens = dens != nullptr;
+    return PMX_OK;
+}
+
 template <typename T>
 int robust_scale_impl(pmx_ctx* c, int pos, double* scale) {
     if (pos < 0 || pos >= kMaxChain || !c->d_rob) return fail(c, PMX_E_STATE, "no RobustOutlierFilter scale at this position");
@@ -1624,6 +1667,94 @@ int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* p
     return PMX_OK;
 }
 
+// ErrorMinimizer::getResidualError / getOverlap for the resident match, its
+// chain record and step transform (pmx_quality.h): the chain's weights are
+// materialised as for the host mirror, then two reductions of their own
+// behind the covariance's sums.  Never inside a loop.
+template <typename T>
+int quality_impl(pmx_ctx* c, const T* Tm_host, int minimizer, pmx_quality* out) {
+    using L = QualitySums;
+    if (minimizer < 0 || minimizer > 3) return fail(c, PMX_E_BAD_PARAM, "pmx_match_quality: minimizer must be 0 to 3");
+    const bool plane = minimizer == 0 || minimizer == 2;
+    int rc = check_match(c);
+    if (rc) return rc;
+    if (plane && !c->has_normals)
+        return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer requires \"normals\" on the reference");
+    HIPCHK(c, hipSetDevice(c->device));
+    int branch = kQBNone;
+    if (plane) {
+        if (c->has_rnoise && c->has_ref_noise) branch = c->has_ref_dens ? kQBDensity : kQBBoth;
+        else if (c->has_rnoise) branch = kQBReading;
+        else if (c->has_ref_noise) branch = kQBReference;
+    } else if (c->has_rnoise) {
+        branch = kQBReading;
+    }
+    if (branch == kQBDensity && c->nranks > 1)
+        return fail(c, PMX_E_BAD_PARAM,
+                    "pmx_match_quality: the median density of the kept links over several ranks is not supported");
+    std::memset(out, 0, sizeof(*out));
+    const int64_t n = c->N * c->knn;
+    if ((rc = materialise_weights<T>(c))) return rc;
+    QualityIn<T> in{};
+    in.rd = (const P4<T>*)c->d_rd;
+    in.ref = (const P4<T>*)match_pn(c);
+    in.nrm = (const P4<T>*)match_nrm(c);
+    in.rs = match_rs(c);
+    in.d = (const T*)c->d_dists;
+    in.ids = c->d_ids;
+    in.w = (const T*)c->d_w;
+    in.k = c->knn;
+    in.N = c->N;
+    in.nbr = plane && nbr_with_normals(c) ? (const P4<T>*)c->d_nbr : nullptr;
+    in.gidx = c->ids_grid ? c->lv(c->ids_level).gidx : nullptr;
+    in.noise_rd = c->has_rnoise ? (const T*)c->d_rnoise : nullptr;
+    in.noise_ref = c->has_ref_noise ? (const T*)c->d_ref_noise : nullptr;
+    in.dens_ref = c->has_ref_dens ? (const T*)c->d_ref_dens : nullptr;
+    const Mat4<T> Tm = Tm_host ? embed<T>(Tm_host, c->rows) : step_mat<T>(c);
+    T* keys = nullptr;
+    if (branch == kQBDensity && n > 0) HIPCHK(c, hipMalloc((void**)&keys, sizeof(T) * (size_t)n));
+    struct FreeKeys {
+        T* p;
+        ~FreeKeys() {
+            if (p) (void)hipFree(p);
+        }
+    } free_keys{keys};
+    double r[L::kNV] = {};
+    launch_match_quality<T>(in, Tm, plane, keys, c->d_partials, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = finish_sums(c, {c->d_result + L::kAt, L::kPass1NV}))) return rc;  // (several ranks: one collective)
+    HIPCHK(c, hipMemcpyAsync(r, c->d_result + L::kAt, sizeof(double) * L::kPass1NV, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t links = (int64_t)r[L::kLinks];
+    out->residual = r[L::kResidual];
+    out->links = links;
+    out->dist_sum = r[L::kSqrtSum];
+    out->branch = branch;
+    // (no noise, or no column at all: the reference divides only when links exist)
+    if (branch == kQBNone || links == 0) return PMX_OK;
+    T base = 0;
+    if (plane) {
+        if (branch == kQBDensity) {
+            T med = 0;
+            HIPCHK(c, quality_median<T>(keys, n, links, &med, c->stream));
+            out->median_density = (double)med;
+            base = (T)(1.0 / std::pow((double)med, 1 / 3.0));  // medianRadius, PointToPlane.cpp:402
+        }
+        out->overlap_den = (int64_t)r[L::kPoints] + (int64_t)r[L::kRejPoints];  // :464
+    } else {
+        base = (T)(r[L::kSqrtSum] / (double)links);  // mean, PointToPoint.cpp:140
+        out->overlap_den = links;
+    }
+    launch_match_overlap<T>(in, plane, branch, base, c->d_partials, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = finish_sums(c, {c->d_result + L::kAt + L::kHits, 1}))) return rc;
+    HIPCHK(c, hipMemcpyAsync(r + L::kHits, c->d_result + L::kAt + L::kHits, sizeof(double), hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->overlap_num = (int64_t)r[L::kHits];
+    return PMX_OK;
+}
+
 template <typename T>
 int get_matches_impl(pmx_ctx* c, void* dists, int32_t* ids) {
     int rc = check_match(c);
@@ -1680,6 +1811,7 @@ int get_weights_impl(pmx_ctx* c, void* w) {
     template int p2plane_enqueue<T>(pmx_ctx*, PendingSums*);                                \
     template int p2point_enqueue<T>(pmx_ctx*, bool, PendingSums*);                          \
     template int p2plane_cov_impl<T>(pmx_ctx*, const T*, double*, double*, int64_t*);       \
+    template int quality_impl<T>(pmx_ctx*, const T*, int, pmx_quality*);                    \
     template int get_matches_impl<T>(pmx_ctx*, void*, int32_t*);                            \
     template int unpermute<T>(pmx_ctx*, const std::vector<T>&, T*, int);
 PMX_INST(float)
@@ -1743,6 +1875,20 @@ int pmx_set_reading_normals(pmx_ctx* c, const void* normals) {
                     set_reading_normals_impl<double>(c, (const double*)normals));
 }
 
+int pmx_set_reading_noise(pmx_ctx* c, const void* noise) {
+    if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c, set_reading_noise_impl<float>(c, (const float*)noise),
+                    set_reading_noise_impl<double>(c, (const double*)noise));
+}
+
+int pmx_set_reference_descriptors(pmx_ctx* c, const void* noise, const void* densities) {
+    if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c, set_reference_descriptors_impl<float>(c, (const float*)noise, (const float*)densities),
+                    set_reference_descriptors_impl<double>(c, (const double*)noise, (const double*)densities));
+}
+
 int pmx_match(pmx_ctx* c, const void* T_iter, int knn, double maxDist, double epsilon, uint64_t* visited) {
     if (!c || !T_iter) return fail(c, PMX_E_BAD_PARAM, "null argument");
     if (!(epsilon >= 0)) return fail(c, PMX_E_BAD_PARAM, "epsilon must be >= 0");
@@ -1772,6 +1918,12 @@ int pmx_p2plane_covariance(pmx_ctx* c, const void* T_step, double* H, double* Q,
     if (!c || !T_step || !H || !Q) return fail(c, PMX_E_BAD_PARAM, "null argument");
     return DISPATCH(c, p2plane_cov_impl<float>(c, (const float*)T_step, H, Q, pairs),
                     p2plane_cov_impl<double>(c, (const double*)T_step, H, Q, pairs));
+}
+
+int pmx_match_quality(pmx_ctx* c, const void* T_step, int minimizer, pmx_quality* out) {
+    if (!c || !out) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    return DISPATCH(c, quality_impl<float>(c, (const float*)T_step, minimizer, out),
+                    quality_impl<double>(c, (const double*)T_step, minimizer, out));
 }
 
 int pmx_p2point_system(pmx_ctx* c, double* mp, double* mq, double* m, pmx_stats* st) {

@@ -13,6 +13,7 @@
 #include "pmx_internal.h"
 #include "pmx_p2plane.h"
 #include "pmx_cov.h"
+#include "pmx_quality.h"
 #include "pmx_spec.h"
 
 #include <rccl/rccl.h>
@@ -200,6 +201,17 @@ struct pmx_ctx {
     size_t rnrm_bytes = 0;
     const void* d_rnrm_p4 = nullptr;  // (the records, inside d_rnrm)
     bool has_rnrm = false;
+    // getOverlap's descriptors (pmx_quality.h): the reading's simpleSensorNoise
+    // in slot order (pmx_set_reading_noise: T[N], then the upload half), the
+    // reference's simpleSensorNoise and densities in original id order
+    // (pmx_set_reference_descriptors: T[M] each)
+    void* d_rnoise = nullptr;
+    size_t rnoise_bytes = 0;
+    bool has_rnoise = false;
+    void* d_ref_noise = nullptr;
+    void* d_ref_dens = nullptr;
+    size_t ref_noise_bytes = 0, ref_dens_bytes = 0;
+    bool has_ref_noise = false, has_ref_dens = false;
 
     // matches / weights
     int knn = 0;
@@ -425,6 +437,9 @@ template <typename T>
 int p2point_enqueue(pmx_ctx* c, bool similarity, PendingSums* last);
 template <typename T>
 int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* pairs);
+// pmx_match_quality on the resident match; Tm (rows x rows row-major T; null: the match's own) the step transform
+template <typename T>
+int quality_impl(pmx_ctx* c, const T* Tm, int minimizer, pmx_quality* out);
 template <typename T>
 int get_matches_impl(pmx_ctx* c, void* dists, int32_t* ids);
 template <typename V>

@@ -500,6 +500,18 @@ int loop_cov_impl(pmx_ctx* c, double* H, double* Q, int64_t* pairs) {
     return p2plane_cov_impl<T>(c, dT, H, Q, pairs);
 }
 
+// pmx_loop_quality: as pmx_loop_covariance, the stopped loop's last match,
+// limits and step transform (Tstep, from LoopCtl::Tprev) are resident
+template <typename T>
+int loop_quality_impl(pmx_ctx* c, int minimizer, pmx_quality* out) {
+    if (!c->loop_begun || !c->loop_done || c->loop_err)
+        return fail(c, PMX_E_STATE, "pmx_loop_quality: the device loop has not finished, or stopped on an error");
+    // (iterations enqueued after the device stopped may have materialised weights
+    // with the host's transform of that moment: take them again at Tstep)
+    c->w_valid = false;
+    return quality_impl<T>(c, nullptr, minimizer, out);
+}
+
 template <typename T>
 int loop_trace_impl(pmx_ctx* c, int first, int count, void* out) {
     if (!c->loop_begun || !c->loop_cfg.keep_trace) return fail(c, PMX_E_STATE, "no loop trace (keep_trace = 0)");
@@ -534,6 +546,12 @@ int pmx_loop_covariance(pmx_ctx* c, double* H, double* Q, int64_t* pairs) {
     if (!c || !H || !Q) return fail(c, PMX_E_BAD_PARAM, "null argument");
     (void)hipSetDevice(c->device);
     return DISPATCH(c, loop_cov_impl<float>(c, H, Q, pairs), loop_cov_impl<double>(c, H, Q, pairs));
+}
+
+int pmx_loop_quality(pmx_ctx* c, int minimizer, pmx_quality* out) {
+    if (!c || !out) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c, loop_quality_impl<float>(c, minimizer, out), loop_quality_impl<double>(c, minimizer, out));
 }
 
 int pmx_loop_trace(pmx_ctx* c, int first, int count, void* out) {

@@ -1,8 +1,9 @@
 // pmx_sums.h — the layout of the error minimisers' sums, once, for host and
 // device: the reduction kernels' accumulators (pmx_reduce.hip, pmx_p2plane.h,
-// pmx_cov.hip), the result area they are finalized into (pmx_ctx.d_result) and
-// its readers, the device step (pmx_step.h) and the host readback (pmx_chain.hip).
-// Accumulator v lands at result[base + v]; base is 0, kPass2At or kCovAt.
+// pmx_cov.hip, pmx_quality.hip), the result area they are finalized into
+// (pmx_ctx.d_result) and its readers, the device step (pmx_step.h) and the host
+// readback (pmx_chain.hip).
+// Accumulator v lands at result[base + v]; base is 0, kPass2At, kCovAt or QualitySums::kAt.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -59,6 +60,14 @@ constexpr int kCovCount = kCovTri;
 constexpr int kCovQ = kCovTri + 1;
 constexpr int kCovNV = 2 * kCovTri + 1;
 
+// getResidualError / getOverlap of the last match (pmx_quality.hip), behind the
+// covariance: the first pass's sums over the kept links, then the second
+// pass's count (the reading points hit, or point-to-point's links inside).
+struct QualitySums {
+    static constexpr int kAt = 112;
+    enum { kResidual, kLinks, kSqrtSum, kPoints, kRejPoints, kPass1NV, kHits = kPass1NV, kNV };
+};
+
 static_assert(P2PointSums::kPass1NV == 11 && P2PointSums::kMomentsNV == 20 && P2PointSums::kSigma == 25, "layout");
 static_assert(P2PlaneSums<3, true>::NV <= kNVMax && P2PlaneSums<3, false>::NV <= kNVMax &&
                   P2PlaneSums<2, true>::NV <= kNVMax && P2PlaneSums<2, false>::NV <= kNVMax &&
@@ -69,6 +78,9 @@ static_assert(kStepRes == 48 && P2PlaneSums<3, true>::NV <= kStepRes && P2PointS
               "the step reads the first kStepRes doubles");
 static_assert(P2PointSums::kPass1NV <= P2PointSums::kPass2At, "pass 1 ends before the second pass's sums");
 static_assert(kStepRes <= kCovAt && kCovAt + kCovNV <= kResultDoubles, "the covariance behind the step's area");
+static_assert(kCovAt + kCovNV <= QualitySums::kAt && QualitySums::kAt + QualitySums::kNV <= kResultDoubles &&
+                  QualitySums::kNV <= kNVMax,
+              "the quality sums behind the covariance");
 
 // The five statistics of a form's sums.
 template <int DIM>

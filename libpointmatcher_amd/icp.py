@@ -86,6 +86,10 @@ def lib():
         l.pmx_icp_stats_get.argtypes = [C.c_void_p, C.POINTER(IcpStats)]
         l.pmx_icp_trace_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         l.pmx_icp_covariance.argtypes = [C.c_void_p, C.c_void_p]
+        l.pmx_icp_overlap.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        l.pmx_icp_residual_error.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        l.pmx_icp_filtered_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_char_p,
+                                                  C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         l.pmx_icp_timing.argtypes = [C.c_void_p, C.c_int]
         l.pmx_icp_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         l.pmx_icp_select_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -269,6 +273,35 @@ class ICP:
         out = np.zeros((6, 6), self.dtype)
         self._chk(self._l.pmx_icp_covariance(self.h, _p(out)))
         return out
+
+    def overlap(self):
+        """errorMinimizer->getOverlap() of the last compute (pmx_icp_overlap): from
+        the clouds' simpleSensorNoise / densities when present, else the weighted
+        used ratio."""
+        v = C.c_double()
+        self._chk(self._l.pmx_icp_overlap(self.h, C.byref(v)))
+        return v.value
+
+    def residual_error(self):
+        """errorMinimizer->getResidualError() of the last compute (pmx_icp_residual_error)."""
+        v = C.c_double()
+        self._chk(self._l.pmx_icp_residual_error(self.h, C.byref(v)))
+        return v.value
+
+    def filtered_descriptor(self, cloud, points, name):
+        """The descriptor `name` of `points` after the chain's reading
+        ("reading") or reference filters (pmx_icp_filtered_descriptor): (n, span)
+        array, or None when the filtered cloud has no such descriptor."""
+        pts = np.ascontiguousarray(points, dtype=self.dtype)
+        which = 0 if cloud == "reading" else 1
+        n, span = C.c_int64(0), C.c_int(0)
+        # (sized by the caller's cloud: filters only remove points; span <= 16 covers every descriptor here)
+        out = np.empty(pts.shape[0] * 16, self.dtype)
+        self._chk(self._l.pmx_icp_filtered_descriptor(self.h, which, _p(pts), pts.shape[1], pts.shape[0],
+                                                      name.encode(), _p(out), out.size, C.byref(n), C.byref(span)))
+        if span.value == 0:
+            return None
+        return out[:n.value * span.value].reshape(n.value, span.value).copy()
 
     def timing(self, on=True):
         self._chk(self._l.pmx_icp_timing(self.h, 1 if on else 0))
