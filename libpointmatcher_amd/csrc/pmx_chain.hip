@@ -986,15 +986,36 @@ int check_match(pmx_ctx* c) {
     return PMX_OK;
 }
 
-// the reference layout the current match ids index
-const void* match_ref(const pmx_ctx* c) { return c->ids_grid ? c->lv(c->ids_level).gpts : c->d_ref; }
-// the point-to-plane gather: a grid level's interleaved records (stride 2)
-// or the reference and its normals (stride 1)
-const void* match_pn(const pmx_ctx* c) { return c->ids_grid ? c->lv(c->ids_level).gpn : c->d_ref; }
-const void* match_nrm(const pmx_ctx* c) {
-    return c->ids_grid ? (const void*)((const char*)c->lv(c->ids_level).gpn + (c->dtype == PMX_F64 ? 32 : 16)) : c->d_nrm;
+// The resident match as the reductions read it (MatchView, pmx_internal.h):
+// the one place that knows which arrays the current ids index.  After a grid
+// match they are positions in the level's records (points: gpts; point and
+// normal interleaved: gpn, stride 2), after a brute-force match reference
+// indices (d_ref and d_nrm, stride 1).
+template <typename T>
+MatchView<T> match_view(const pmx_ctx* c) {
+    MatchView<T> m{};
+    m.rd = (const P4<T>*)c->d_rd;
+    m.d = (const T*)c->d_dists;
+    m.ids = c->d_ids;
+    m.k = c->knn;
+    m.N = c->N;
+    if (c->ids_grid) {
+        const auto& lv = c->lv(c->ids_level);
+        m.ref = (const P4<T>*)lv.gpts;
+        m.pn = (const P4<T>*)lv.gpn;
+        m.nrm = m.pn ? m.pn + 1 : nullptr;  // (null: a reference without normals)
+        m.rs = 2;
+        m.gidx = lv.gidx;
+        // k = 1 after a match that left its neighbour records with the normals
+        // (d_nbr: points, then normals, in slot order)
+        if (c->nbr_prev && c->nbr_normals && c->knn == 1) m.nbr = (const P4<T>*)c->d_nbr;
+    } else {
+        m.ref = m.pn = (const P4<T>*)c->d_ref;
+        m.nrm = (const P4<T>*)c->d_nrm;
+        m.rs = 1;
+    }
+    return m;
 }
-int match_rs(const pmx_ctx* c) { return c->ids_grid ? 2 : 1; }
 
 // Adaptive grid level for the next match, from the pairs this match
 // evaluated per query and per point-per-cell (~ occupied cells visited):
@@ -1107,8 +1128,9 @@ WChain<T> chain_of(const pmx_ctx* c) {
             const T eps = (T)c->chain_thr[i];
             w.sn.eps = w.sn.rn && !(eps > w.sn.eps) ? w.sn.eps : eps;
             w.sn.rn = (const P4<T>*)c->d_rnrm_p4;
-            w.sn.nrm = (const P4<T>*)match_nrm(c);
-            w.sn.rs = match_rs(c);
+            const MatchView<T> m = match_view<T>(c);
+            w.sn.nrm = m.nrm;
+            w.sn.rs = m.rs;
             w.sn.dim = c->dim;
         }
     }
@@ -1220,7 +1242,7 @@ int outlier_impl(pmx_ctx* c, int kind, int chain_pos, double p0, double p1, doub
         chain_set(c, chain_pos, kWPState, 1.0);
         break;
     }
-    case 8:  // SurfaceNormal: p0 = eps = cos(maxAngle) in T; reads no distance (pmx_snormal.h)
+    case 8:  // SurfaceNormal: p0 = eps = cos(maxAngle) in T; reads no distance (sn_pass, pmx_weight.h)
         chain_set(c, chain_pos, kWPNormal, (double)(T)p0);
         break;
     default:
@@ -1477,23 +1499,12 @@ void after_readback(pmx_ctx* c) {
     choose_level(c, v, f);
 }
 
-// k = 1 after a grid match that left its neighbour records with the normals
-// (d_nbr: points, then normals, in slot order)
-bool nbr_with_normals(const pmx_ctx* c) { return c->nbr_prev && c->nbr_normals && c->knn == 1 && c->ids_grid; }
-
-// the chain's weights into d_w (the host mirror; a point-to-plane robust
-// distance under the point-to-point minimiser)
+// the chain's weights into d_w (the host mirror and the quality reductions;
+// a point-to-plane robust distance under the point-to-point minimiser)
 template <typename T>
 int materialise_weights(pmx_ctx* c) {
     if (c->w_valid) return PMX_OK;
-    const WChain<T> chain = chain_of<T>(c);
-    const Mat4<T> Tm = step_mat<T>(c);
-    launch_weights_chain<T>((const T*)c->d_dists, (T*)c->d_w, c->N * c->knn, chain, (const P4<T>*)c->d_rd, Tm,
-                            (const P4<T>*)match_pn(c), (const P4<T>*)match_nrm(c), match_rs(c), c->d_ids, c->knn,
-                            c->stream);
-    if (chain.sn.rn)  // the SurfaceNormalOutlierFilter's factor (pmx_snormal.hip)
-        launch_sn_weights<T>((T*)c->d_w, c->N * c->knn, c->knn, chain.sn, Tm, c->d_ids,
-                             nbr_with_normals(c) ? (const P4<T>*)c->d_nbr + c->N : nullptr, c->stream);
+    launch_weights_chain<T>(match_view<T>(c), step_mat<T>(c), chain_of<T>(c), (T*)c->d_w, c->stream);
     HIPCHK(c, hipGetLastError());
     c->w_valid = true;
     return PMX_OK;
@@ -1510,14 +1521,8 @@ int finish_sums(pmx_ctx* c, const PendingSums& p) {
 template <typename T>
 int p2plane_enqueue(pmx_ctx* c, PendingSums* last) {
     const WChain<T> chain = chain_of<T>(c);
-    Mat4<T> Tm = step_mat<T>(c);
-    // (k = 1 after a match that left its neighbour records with normals:
-    // the reduction reads them in slot order instead of gathering by id)
-    const bool nbr = nbr_with_normals(c) && !chain.robust;
-    launch_p2plane_partial<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_pn(c), (const P4<T>*)match_nrm(c),
-                              match_rs(c), (const T*)c->d_dists, c->d_ids, chain, c->knn, c->N, c->dim, c->d_partials,
-                              loop_ctl(c), (const GridDesc<T>*)c->d_gdesc, c->vpart_dirty ? c->d_vpart : nullptr,
-                              c->stream, nbr ? (const P4<T>*)c->d_nbr : nullptr);
+    launch_p2plane_partial<T>(match_view<T>(c), step_mat<T>(c), chain, c->dim, c->d_partials, loop_ctl(c),
+                              (const GridDesc<T>*)c->d_gdesc, c->vpart_dirty ? c->d_vpart : nullptr, c->stream);
     c->vpart_dirty = false;
     HIPCHK(c, hipGetLastError());
     *last = {c->d_result, p2plane_nv(c->dim, chain.robust)};
@@ -1532,7 +1537,8 @@ int p2plane_enqueue(pmx_ctx* c, PendingSums* last) {
 template <typename T>
 int p2point_enqueue(pmx_ctx* c, bool similarity, PendingSums* last) {
     using L = P2PointSums;
-    Mat4<T> Tm = step_mat<T>(c);
+    const MatchView<T> m = match_view<T>(c);
+    const Mat4<T> Tm = step_mat<T>(c);
     WChain<T> chain = chain_of<T>(c);
     int rc;
     if (chain.robust && chain.rb_p2pl) {  // (the point-to-point kernels carry no normals)
@@ -1543,19 +1549,16 @@ int p2point_enqueue(pmx_ctx* c, bool similarity, PendingSums* last) {
     if (c->loop_on && c->loop_dev.p2p_onepass && !similarity) {
         // device loop: both passes' sums in one read of the matches, the
         // step centres the moments (LoopCfg.p2p_onepass)
-        launch_p2point_moments<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists,
-                                  c->d_ids, chain, c->knn, c->N, c->d_partials, loop_ctl(c), gd, c->stream);
+        launch_p2point_moments<T>(m, Tm, chain, c->d_partials, loop_ctl(c), gd, c->stream);
         HIPCHK(c, hipGetLastError());
         *last = {c->d_result, L::kMomentsNV};
         return PMX_OK;
     }
-    launch_p2point_pass1<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists, c->d_ids,
-                            chain, c->knn, c->N, c->d_partials, loop_ctl(c), gd, c->stream);
+    launch_p2point_pass1<T>(m, Tm, chain, c->d_partials, loop_ctl(c), gd, c->stream);
     if ((rc = finish_sums(c, {c->d_result, L::kPass1NV}))) return rc;
     launch_p2point_means<T>(c->d_result, (T*)c->d_means, c->dim, loop_ctl(c), c->stream);
-    launch_p2point_pass2<T>((const P4<T>*)c->d_rd, Tm, (const P4<T>*)match_ref(c), (const T*)c->d_dists, c->d_ids,
-                            chain, c->knn, c->N, (const T*)c->d_means, c->d_partials, loop_ctl(c), gd, c->stream,
-                            similarity);
+    launch_p2point_pass2<T>(m, Tm, chain, (const T*)c->d_means, similarity, c->d_partials, loop_ctl(c), gd,
+                            c->stream);
     HIPCHK(c, hipGetLastError());
     // (sigma rides in the moments' exchange: no extra collective)
     *last = {c->d_result + L::kPass2At, similarity ? L::kPass2SimNV : L::kPass2NV};
@@ -1645,14 +1648,10 @@ int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* p
     cp.tx = Tinc[0 * R + 3];
     cp.ty = Tinc[1 * R + 3];
     cp.tz = Tinc[2 * R + 3];
-    const WChain<T> chain = chain_of<T>(c);
-    const bool nbr = nbr_with_normals(c) && !chain.robust;  // (the records p2plane_enqueue reads)
     // the second half of the iteration block's result area: the step's
     // system and the statistics in the first half stay as the minimiser left them
     const PendingSums cov = {c->d_result + kCovAt, kCovNV};
-    launch_p2plane_cov<T>((const P4<T>*)c->d_rd, step_mat<T>(c), (const P4<T>*)match_pn(c),
-                          (const P4<T>*)match_nrm(c), match_rs(c), (const T*)c->d_dists, c->d_ids, chain, c->knn, c->N,
-                          cp, c->d_partials, c->stream, nbr ? (const P4<T>*)c->d_nbr : nullptr);
+    launch_p2plane_cov<T>(match_view<T>(c), step_mat<T>(c), chain_of<T>(c), cp, c->d_partials, c->stream);
     if ((rc = finish_sums(c, cov))) return rc;  // (never inside a loop; several ranks: the one extra collective per ICP)
     double r[kCovNV];
     HIPCHK(c, hipMemcpyAsync(r, cov.out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
@@ -1695,21 +1694,9 @@ int quality_impl(pmx_ctx* c, const T* Tm_host, int minimizer, pmx_quality* out) 
     std::memset(out, 0, sizeof(*out));
     const int64_t n = c->N * c->knn;
     if ((rc = materialise_weights<T>(c))) return rc;
-    QualityIn<T> in{};
-    in.rd = (const P4<T>*)c->d_rd;
-    in.ref = (const P4<T>*)match_pn(c);
-    in.nrm = (const P4<T>*)match_nrm(c);
-    in.rs = match_rs(c);
-    in.d = (const T*)c->d_dists;
-    in.ids = c->d_ids;
-    in.w = (const T*)c->d_w;
-    in.k = c->knn;
-    in.N = c->N;
-    in.nbr = plane && nbr_with_normals(c) ? (const P4<T>*)c->d_nbr : nullptr;
-    in.gidx = c->ids_grid ? c->lv(c->ids_level).gidx : nullptr;
-    in.noise_rd = c->has_rnoise ? (const T*)c->d_rnoise : nullptr;
-    in.noise_ref = c->has_ref_noise ? (const T*)c->d_ref_noise : nullptr;
-    in.dens_ref = c->has_ref_dens ? (const T*)c->d_ref_dens : nullptr;
+    const QualityIn<T> in{match_view<T>(c), (const T*)c->d_w, c->has_rnoise ? (const T*)c->d_rnoise : nullptr,
+                          c->has_ref_noise ? (const T*)c->d_ref_noise : nullptr,
+                          c->has_ref_dens ? (const T*)c->d_ref_dens : nullptr};
     const Mat4<T> Tm = Tm_host ? embed<T>(Tm_host, c->rows) : step_mat<T>(c);
     T* keys = nullptr;
     if (branch == kQBDensity && n > 0) HIPCHK(c, hipMalloc((void**)&keys, sizeof(T) * (size_t)n));

@@ -78,11 +78,10 @@ __device__ __forceinline__ void cov_add(double (&acc)[NV], T px, T py, T pz, con
 
 // The reduction over the kept pairs of a 3-D match: per-block partials of the
 // kCovNV values into partials[v * kRedBlocks + block] (launch_finalize sums
-// them).  rd / Tm / ref / nrm / rs / d / ids / chain / k / N / nbr as
-// launch_p2plane_partial; never part of a device-loop iteration (no LoopCtl).
+// them).  m / Tm / chain as launch_p2plane_partial; never part of a
+// device-loop iteration (no LoopCtl).
 template <typename T>
-void launch_p2plane_cov(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const P4<T>* nrm, int rs, const T* d,
-                        const int32_t* ids, const WChain<T>& chain, int k, int64_t N, const CovParams<T>& cp,
-                        double* partials, hipStream_t s, const P4<T>* nbr);
+void launch_p2plane_cov(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, const CovParams<T>& cp,
+                        double* partials, hipStream_t s);
 
 }  // namespace pmx

@@ -19,20 +19,14 @@
 namespace pmx {
 
 // entry (slot i, distance dv, id) is a column of ErrorElements: dist != inf
-// and w != 0 (ErrorMinimizer.cpp:75-131) for the chain's weight w
+// and w != 0 (ErrorMinimizer.cpp:75-131) for the chain's weight w (entry_weight,
+// pmx_weight.h; q, n: the matched records as loaded, rn: the reading's normal)
 template <typename T, bool SN>
 __device__ __forceinline__ bool cov_kept(const WChain<T>& chain, const WRange<T>& wr, const Mat4<T>& Tm, T dv,
                                          int32_t id, const P4<T>& rn, T px, T py, T pz, const P4<T>& q,
                                          const P4<T>& n) {
-    if (dv == (T)__builtin_huge_val() || !chain_keep(wr, dv)) return false;
-    if (SN && !(id >= 0 && sn_pass(chain.sn, Tm, rn, n))) return false;
-    if (chain.robust) {  // (the weight of p2plane_weighted_kernel; the predicates' factor is 1 here)
-        const T dist = chain.rb_p2pl ? p2pl_distance(px, py, pz, q, n) : dv;
-        const T sc = (T)*chain.rb_scale;
-        const T w = robust_weight<T>(chain.rb_fct, chain.rb_k, chain.rb_sqa, dist / (sc * sc));
-        if (w == (T)0) return false;
-    }
-    return true;
+    if (dv == (T)__builtin_huge_val()) return false;
+    return entry_weight<T, SN>(chain, chain.sn, wr, Tm, dv, id, px, py, pz, q, loaded(n), loaded(rn)) != (T)0;
 }
 
 template <typename T, bool SN>
@@ -51,6 +45,9 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
     const WRange<T> wr = chain_resolve(chain);
     const T inf = (T)__builtin_huge_val();
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    // whether an entry's records are worth gathering: without the robust
+    // filter a rejecting predicate makes the weight 0 (with it, 0 * NaN is not)
+    const auto may_keep = [&](T dv) { return dv != inf && (chain.robust || chain_keep(wr, dv)); };
     int64_t i0 = (int64_t)xcd_block() * blockDim.x + threadIdx.x;
     if (k == 1) {
         // k = 1: U slots per round, every load that needs no id issued up
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
             if (!nbr) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const bool gat = i0 + u * stride < N && dv[u] != inf && id[u] >= 0 && chain_keep(wr, dv[u]);
+                    const bool gat = i0 + u * stride < N && id[u] >= 0 && may_keep(dv[u]);
                     const int64_t g = (int64_t)(gat ? id[u] : 0) * rs;  // (position 0 always exists)
                     q[u] = gld(ref, g);
                     n[u] = gld(nrm, g);
@@ -105,7 +102,7 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
             const T dv = d[e];
-            if (dv == inf || !chain_keep(wr, dv)) continue;
+            if (!may_keep(dv)) continue;
             const int32_t id = ids[e];
             const int64_t g = (int64_t)(id >= 0 ? id : 0) * rs;
             const P4<T> q = gld(ref, g), n = gld(nrm, g);
@@ -118,19 +115,18 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
 }
 
 template <typename T>
-void launch_p2plane_cov(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const P4<T>* nrm, int rs, const T* d,
-                        const int32_t* ids, const WChain<T>& chain, int k, int64_t N, const CovParams<T>& cp,
-                        double* partials, hipStream_t s, const P4<T>* nbr) {
+void launch_p2plane_cov(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, const CovParams<T>& cp,
+                        double* partials, hipStream_t s) {
     auto* const kern = chain.sn.rn ? p2plane_cov_kernel<T, true> : p2plane_cov_kernel<T, false>;
-    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm, rs, d, ids, chain, k, N, cp.alpha,
-                       cp.beta, cp.gamma, cp.tx, cp.ty, cp.tz, partials, k == 1 ? nbr : nullptr);
+    // (the neighbour records where the last point-to-plane reduction read them: k = 1, no robust filter)
+    const P4<T>* nbr = m.k == 1 && !chain.robust ? m.nbr : nullptr;
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k, m.N,
+                       cp.alpha, cp.beta, cp.gamma, cp.tx, cp.ty, cp.tz, partials, nbr);
 }
 
-template void launch_p2plane_cov<float>(const P4<float>*, const Mat4<float>&, const P4<float>*, const P4<float>*, int,
-                                        const float*, const int32_t*, const WChain<float>&, int, int64_t,
-                                        const CovParams<float>&, double*, hipStream_t, const P4<float>*);
-template void launch_p2plane_cov<double>(const P4<double>*, const Mat4<double>&, const P4<double>*, const P4<double>*,
-                                         int, const double*, const int32_t*, const WChain<double>&, int, int64_t,
-                                         const CovParams<double>&, double*, hipStream_t, const P4<double>*);
+template void launch_p2plane_cov<float>(const MatchView<float>&, const Mat4<float>&, const WChain<float>&,
+                                        const CovParams<float>&, double*, hipStream_t);
+template void launch_p2plane_cov<double>(const MatchView<double>&, const Mat4<double>&, const WChain<double>&,
+                                         const CovParams<double>&, double*, hipStream_t);
 
 }  // namespace pmx

@@ -319,122 +319,12 @@ void launch_surface_normals(const P4<T>* pts, const P4<T>* gpts, const int32_t* 
 size_t grid_counter_bytes();
 void launch_pos_to_index(const int32_t* pos, const int32_t* gidx, int32_t* out, int64_t n, hipStream_t s);
 
-// ---- outlier weights as a predicate chain ----
-// Every supported OutlierFilter produces 0/1 weights and a chain multiplies
-// them (OutlierFilter.cpp:63-103), so the chain is a conjunction of
-// predicates on the distance.  It is evaluated inline by the reductions (no
-// weight array is written or read on the hot path) and materialised only for
-// the host mirror (pmx_get_weights).
-// The RobustOutlierFilter (OutlierFiltersImpl.cpp:394-598) is the one
-// filter with real-valued weights: w = robust(e^2), e^2 = dist / scale^2,
-// multiplied with the predicates' 0/1 (kWPRobust, at most one per chain; the
-// reductions take the weighted path only then).
-// The SurfaceNormalOutlierFilter (OutlierFiltersImpl.cpp:225-285) is the one
-// predicate that reads no distance (kWPNormal): it compares the reading's and
-// the matched reference point's normals (SNPred, pmx_snormal.h).  The
-// reductions evaluate it in instantiations of their own, selected at launch
-// when the chain holds it.
-enum WPred { kWPDefault = 0, kWPNull = 1, kWPLe = 2, kWPGe = 3, kWPState = 4, kWPRobust = 5, kWPNormal = 6 };
-// rn != null: the filter is in the chain and both clouds carry normals.
-template <typename T>
-struct SNPred {
-    const P4<T>* rn = nullptr;   // [N]: the reading's normals, rotated by T_refMean_dataIn, slot order
-    const P4<T>* nrm = nullptr;  // the reference normal records the match ids index (device loop: from GridDesc)
-    int rs = 1;                 // their index stride (2: a grid level's interleaved records)
-    int dim = 3;
-    T eps = 0;                  // cos(maxAngle) in T (several filters: the largest)
-};
-enum RobustFct { kRFCauchy = 0, kRFWelsch = 1, kRFSC = 2, kRFGM = 3, kRFTukey = 4, kRFHuber = 5, kRFL1 = 6,
-                 kRFStudent = 7 };
-constexpr int kMaxChain = 8;
-template <typename T>
-struct WChain {
-    int n = 0;
-    int type[kMaxChain] = {};
-    T thr[kMaxChain] = {};                        // kWPLe / kWPGe: threshold; kWPState: scale
-    const SelectState* st[kMaxChain] = {};        // kWPState: resolved quantile (limit)
-    // kWPRobust (robust != 0): function, tuning k, squared approximation,
-    // the scale (device, T value), point-to-plane distance
-    int robust = 0;
-    int rb_fct = 0;
-    T rb_k = 1;
-    T rb_sqa = 0;
-    const double* rb_scale = nullptr;
-    int rb_p2pl = 0;
-    const T* w_arr = nullptr;  // materialised weights (a robust point-to-plane distance, point-to-point minimiser)
-    SNPred<T> sn;              // kWPNormal
-};
-// robustFiltering's weight of one scaled squared error (OutlierFiltersImpl.cpp:541-596)
-template <typename T>
-__device__ __forceinline__ T robust_weight(int fct, T k, T sqa, T e2) {
-    const T k2 = k * k;
-    T w;
-    switch (fct) {
-    case kRFCauchy: w = (T)1 / ((T)1 + e2 / k2); break;
-    case kRFWelsch: w = exp(-e2 / k2); break;
-    case kRFSC: {
-        const T s = k + e2;
-        w = e2 >= k ? (T)(4.0 * (double)k2) * ((T)1 / (s * s)) : (T)1;
-        break;
-    }
-    case kRFGM: {
-        const T s = k + e2;
-        w = k2 * ((T)1 / (s * s));
-        break;
-    }
-    case kRFTukey: {
-        const T a = (T)1 - e2 / k2;
-        w = e2 >= k2 ? (T)0 : a * a;
-        break;
-    }
-    case kRFHuber: w = e2 >= k2 ? k * ((T)1 / sqrt(e2)) : (T)1; break;
-    case kRFL1: w = (T)1 / sqrt(e2); break;
-    default: {  // Student, d = 3
-        const T d = 3;
-        const T p = pow((T)1 + e2 / k, -(k + d) / (T)2);
-        w = p * (k + d) * ((T)1 / (k + e2));
-        break;
-    }
-    }
-    // ARBITRARY_SMALL_VALUE (1e-50 as T: 0 in float), then the approximation
-    const T tiny = (T)1e-50;
-    w = w <= tiny ? tiny : w;
-    if (sqa != (T)__builtin_huge_val() && e2 >= sqa) w = 0;
-    return w;
-}
-// per-thread resolved thresholds (kWPState: scale * limit in T, as the
-// reference's `factor * quantile`, OutlierFiltersImpl.cpp:121-122)
-// A conjunction of `d <= t` / `d >= t` / `d != inf` predicates is one
-// interval test: keep = (d != inf if required) && lo <= d && d <= hi with
-// hi = min of the upper thresholds, lo = max of the lower ones.  A NaN
-// threshold (failed quantile) rejects everything, as `d <= NaN` does; the
-// min/max below propagate it.
-template <typename T>
-struct WRange {
-    T lo, hi;
-    bool finite;
-};
-template <typename T>
-__device__ __forceinline__ WRange<T> chain_resolve(const WChain<T>& c) {
-    WRange<T> r{-(T)__builtin_huge_val(), (T)__builtin_huge_val(), false};
-    for (int i = 0; i < c.n; ++i) {  // uniform, once per thread
-        const int t = c.type[i];
-        if (t == kWPDefault) {
-            r.finite = true;
-        } else if (t == kWPGe) {
-            const T v = c.thr[i];
-            r.lo = (v != v || r.lo != r.lo) ? v + r.lo : (v > r.lo ? v : r.lo);
-        } else if (t == kWPLe || t == kWPState) {
-            const T v = t == kWPState ? c.thr[i] * (T)c.st[i]->limit : c.thr[i];
-            r.hi = (v != v || r.hi != r.hi) ? v + r.hi : (v < r.hi ? v : r.hi);
-        }
-    }
-    return r;
-}
-template <typename T>
-__device__ __forceinline__ bool chain_keep(const WRange<T>& r, T d) {
-    return (!r.finite || d != (T)__builtin_huge_val()) && d >= r.lo && d <= r.hi;
-}
+}  // namespace pmx
+
+// ---- the outlier chain and the weight of one match entry ----
+#include "pmx_weight.h"
+
+namespace pmx {
 
 // ---- SurfaceNormalOutlierFilter (pmx_snormal.hip) ----
 // the reading's normals (raw: D x n point-major) as resident records in slot
@@ -442,11 +332,6 @@ __device__ __forceinline__ bool chain_keep(const WRange<T>& r, T d) {
 template <typename T>
 void launch_reading_normals(const T* raw, int D, const int32_t* order, int64_t n, const Mat4<T>& M0, P4<T>* out,
                             hipStream_t s);
-// w[e] *= the filter's 0/1 (the materialised weights, n = N * k entries);
-// nbr_n (may be null): the k = 1 neighbour records' normals, in slot order
-template <typename T>
-void launch_sn_weights(T* w, int64_t n, int k, const SNPred<T>& p, const Mat4<T>& Tm, const int32_t* ids,
-                       const P4<T>* nbr_n, hipStream_t s);
 
 // ---- robust scale estimators (pmx_robust.hip) ----
 // the exact median index count / 2 (Matches::getMedianAbsDeviation's
@@ -513,41 +398,64 @@ size_t vartrim_scratch_bytes(int64_t n);
 size_t vartrim_scratch_head();  // leading bytes of that scratch that must be zero at allocation
 int vartrim_hdr_copy();     // int offset of the last call's counters in that scratch (pmx_vartrim_partial_sums)
 
+// ---- the resident match (host side) ----
+// What every reduction reads of the last match, built in one place
+// (match_view, pmx_chain.hip).  The struct stops at the launchers: they unpack
+// it, and the hot kernels keep written-out parameters (a struct passed to a
+// kernel by value cost a VGPR and 2 % on the device loop: DESIGN.md, "The
+// grid match's plan").
+template <typename T>
+struct MatchView {
+    const P4<T>* rd;   // the reading, slot order
+    const P4<T>* ref;  // the points the ids index (point-to-point gather)
+    // the point-to-plane gather: point and normal records with index stride
+    // rs (2: a grid level's interleaved records, nrm = pn + 1; 1: the
+    // reference and its normals)
+    const P4<T>* pn;
+    const P4<T>* nrm;
+    int rs;
+    const T* d;
+    const int32_t* ids;
+    int k;
+    int64_t N;
+    // k = 1 after a grid match that left its neighbour records with the
+    // normals (points, then normals at nbr + N, slot order), or null.  Each
+    // launcher decides whether its kernel reads them in place of the gather.
+    const P4<T>* nbr;
+    const int32_t* gidx;  // ids -> original reference ids (null: they are)
+};
+
 // ---- reductions (pmx_reduce.hip) ----
 constexpr int kRedBlocks = 512;  // fixed reduction grid (deterministic sums; 256 / 1024 measured slower)
 // (the layout of every reduction's values: pmx_sums.h)
+// m: the resident match; Tm: the step transform
 // ctl / gd (device loop, may be null): early exit, step transform and the
-// grid level whose positions the ids are (ref / nrm then come from gd)
-// rs: index stride of ref / nrm (1: separate arrays; 2: a grid level's
-// interleaved point / normal records, ref = gpn, nrm = gpn + 1)
+// grid level whose positions the ids are (the records then come from gd)
 // vzero (may be null): the match's spread counters, zeroed by block 0 (a
 // counter phase merged into the select launch read them)
 template <typename T>
-void launch_p2plane_partial(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const P4<T>* nrm, int rs,
-                            const T* d, const int32_t* ids, const WChain<T>& chain, int k, int64_t N, int dim,
+void launch_p2plane_partial(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, int dim,
                             double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, unsigned long long* vzero,
-                            hipStream_t s, const P4<T>* nbr = nullptr);
+                            hipStream_t s);
 void launch_finalize(const double* partials, int nblocks, int nv, double* out, const LoopCtl* ctl, hipStream_t s);
 template <typename T>
-void launch_p2point_pass1(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d,
-                          const int32_t* ids, const WChain<T>& chain, int k, int64_t N, double* partials,
+void launch_p2point_pass1(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, double* partials,
                           const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s);
 template <typename T>
 void launch_p2point_means(const double* sums, T* means_dev, int dim, const LoopCtl* ctl, hipStream_t s);
 // both passes' sums in one (device loop; the step centres the moments,
 // pmx_step.h): P2PointSums::kMomentsNV values
 template <typename T>
-void launch_p2point_moments(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
-                            const WChain<T>& chain, int k, int64_t N, double* partials, const LoopCtl* ctl,
-                            const GridDesc<T>* gd, hipStream_t s);
+void launch_p2point_moments(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, double* partials,
+                            const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s);
 // similarity (PointToPointSimilarity): a tenth sum, sigma (pmx_reduce.hip)
 template <typename T>
-void launch_p2point_pass2(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d,
-                          const int32_t* ids, const WChain<T>& chain, int k, int64_t N, const T* means_dev,
-                          double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s,
-                          bool similarity = false);
+void launch_p2point_pass2(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, const T* means_dev,
+                          bool similarity, double* partials, const LoopCtl* ctl, const GridDesc<T>* gd,
+                          hipStream_t s);
+// the chain's weights of every entry, w[N * k] (entry_weight, the
+// SurfaceNormal factor included): the host mirror and what reads it
 template <typename T>
-void launch_weights_chain(const T* d, T* w, int64_t n, const WChain<T>& chain, const P4<T>* rd, const Mat4<T>& Tm,
-                          const P4<T>* ref, const P4<T>* nrm, int rs, const int32_t* ids, int k, hipStream_t s);
+void launch_weights_chain(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, T* w, hipStream_t s);
 
 }  // namespace pmx

@@ -3,7 +3,6 @@
 #pragma once
 
 #include "pmx_internal.h"
-#include "pmx_snormal.h"
 
 namespace pmx {
 
@@ -12,18 +11,6 @@ __device__ __forceinline__ void xform3(const Mat4<T>& M, const P4<T>& p, T& x, T
     x = ((M.m[0] * p.x + M.m[1] * p.y) + M.m[2] * p.z) + M.m[3] * p.w;
     y = ((M.m[4] * p.x + M.m[5] * p.y) + M.m[6] * p.z) + M.m[7] * p.w;
     z = ((M.m[8] * p.x + M.m[9] * p.y) + M.m[10] * p.z) + M.m[11] * p.w;
-}
-
-// the squared point-to-plane distance of a RobustOutlierFilter with
-// distanceType point2plane (computePointToPlaneDistance,
-// OutlierFiltersImpl.cpp:460-489), with the normalised reference normal
-template <typename T>
-__device__ __forceinline__ T p2pl_distance(T px, T py, T pz, const P4<T>& q, const P4<T>& n) {
-    // Eigen normalized(): v / sqrt(squaredNorm), v itself when the norm is 0
-    const T sq = (n.x * n.x + n.y * n.y) + n.z * n.z;
-    const T nn = sq > (T)0 ? sqrt(sq) : (T)1;
-    const T dot = ((n.x / nn) * (px - q.x) + (n.y / nn) * (py - q.y)) + (n.z / nn) * (pz - q.z);
-    return dot * dot;  // (pow(dot, 2) rounds to the same T)
 }
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -72,9 +59,7 @@ __device__ __forceinline__ bool transpose_writer() {
 
 // block reduction of NV accumulators; writes partials[v * gridDim.x + blockIdx.x]
 // (value-major: the finalize reads each value's block partials contiguously)
-// kCoherent: agent-scope atomic stores (another block of the same launch sums
-// the partials: pmx_post.hip's last-block finalize)
-template <int NV, bool kCoherent = false>
+template <int NV>
 __device__ __forceinline__ void block_store(double (&acc)[NV], double* __restrict__ partials) {
     // (the power of two the transposed wave sum takes)
     constexpr int V = NV <= 8 ? 8 : NV <= 16 ? 16 : NV <= 32 ? 32 : 64;
@@ -90,11 +75,7 @@ __device__ __forceinline__ void block_store(double (&acc)[NV], double* __restric
     __syncthreads();
     for (int v = threadIdx.x; v < NV; v += blockDim.x) {
         const double r = ((red[0][v] + red[1][v]) + red[2][v]) + red[3][v];
-        double* dst = &partials[(int64_t)v * gridDim.x + blockIdx.x];
-        if (kCoherent)
-            __hip_atomic_store(dst, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
-            *dst = r;
+        partials[(int64_t)v * gridDim.x + blockIdx.x] = r;
     }
 }
 
@@ -152,11 +133,15 @@ __device__ __forceinline__ void p2plane_add(double (&acc)[NV], T px, T py, T pz,
 // partials[v * gridDim.x + blockIdx.x]
 // k up to this: the reduction issues a query's k gathers together
 constexpr int kGatherK = 4;
-// SN: the chain holds the SurfaceNormalOutlierFilter (chain.sn, pmx_snormal.h):
+// SN: the chain holds the SurfaceNormalOutlierFilter (chain.sn, pmx_weight.h):
 // every entry's id and the reading's normal are loaded as well, the gathered
 // reference normal serves both the predicate and F, and a pair counts as kept
 // only when both predicates pass (the product of the weights)
-template <typename T, int DIM, bool kCoherent = false, bool SN = false>
+// The keep test below is entry_weight<T, SN>(...) != 0 (pmx_weight.h, the
+// definition) for a chain without the robust filter, which is all this body
+// is launched for: chain_keep(dv) && (!SN || (id >= 0 && sn_pass)).  It stays
+// written out, once per k range, around each range's own order of loads.
+template <typename T, int DIM, bool SN = false>
 __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const Mat4<T>& Tm,
                                              const P4<T>* __restrict__ ref, const P4<T>* __restrict__ nrm, int rs,
                                              const T* __restrict__ d, const int32_t* __restrict__ ids,
@@ -309,7 +294,7 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
         }
         if (!exist) acc[ST + kRejPoints] += 1.0;
     }
-    block_store<NV, kCoherent>(acc, partials);
+    block_store<NV>(acc, partials);
 }
 
 }  // namespace pmx

@@ -5,8 +5,7 @@
 //
 // A link (slot i, rank s) is a column of ErrorElements when dist != inf and
 // w != 0 (ErrorMinimizer.cpp:75-131), w the chain's materialised weight (the
-// mirror's array: every predicate, the SurfaceNormal factor and a robust
-// chain's real weight are in it).  Per kept link, every product and sum in T,
+// mirror's array: entry_weight of every entry, pmx_weight.h).  Per kept link, every product and sum in T,
 // separately rounded, in the reference's order, widened to double and added
 // in fp64:
 //   point-to-plane residual  w * (e * e), e = ((d0 n0) + (d1 n1)) + (d2 n2),
@@ -36,29 +35,20 @@ enum QualityBranch {
     kQBReference = 4 // u = noise_ref[id]
 };
 
-// The resident match and the descriptors the reductions read.  ids index ref /
-// nrm with stride rs (launch_p2plane_partial); gidx (null: ids are reference
-// indices) maps them to the original reference ids the descriptors are in.
+// The resident match (m; point-to-plane reads m.pn / m.nrm, or m.nbr at
+// k = 1), its materialised weights and the descriptors the reductions read;
+// m.gidx maps the ids to the original reference ids the descriptors are in.
 template <typename T>
 struct QualityIn {
-    const P4<T>* rd;
-    const P4<T>* ref;
-    const P4<T>* nrm;
-    int rs;
-    const T* d;
-    const int32_t* ids;
+    MatchView<T> m;
     const T* w;
-    int k;
-    int64_t N;
-    const P4<T>* nbr;      // k = 1: the match's neighbour records (points, then normals), or null
-    const int32_t* gidx;
     const T* noise_rd;     // [N] slot order, or null
     const T* noise_ref;    // [M] original id order, or null
     const T* dens_ref;     // [M] original id order, or null
 };
 
 // First pass: QualitySums::kPass1NV per-block partials.  plane: the
-// point-to-plane residual (needs ref / nrm), else point-to-point's.  keys
+// point-to-plane residual (needs the normals), else point-to-point's.  keys
 // (may be null): [N * k], the reference density of every kept link, +inf for
 // the others (the median's input).
 template <typename T>

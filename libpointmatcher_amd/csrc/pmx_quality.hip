@@ -28,8 +28,8 @@ __device__ __forceinline__ bool quality_kept(const QualityIn<T>& in, int64_t e, 
 // the original reference id of a kept link's match
 template <typename T>
 __device__ __forceinline__ int32_t quality_orig(const QualityIn<T>& in, int64_t e) {
-    const int32_t id = in.ids[e];
-    return in.gidx ? gld(in.gidx, id) : id;
+    const int32_t id = in.m.ids[e];
+    return in.m.gidx ? gld(in.m.gidx, id) : id;
 }
 
 template <typename T, bool PLANE>
@@ -40,15 +40,15 @@ __global__ __launch_bounds__(256) void match_quality_kernel(QualityIn<T> in, Mat
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    const int k = in.k;
+    const int k = in.m.k;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)xcd_block() * blockDim.x + threadIdx.x; i < in.N; i += stride) {
+    for (int64_t i = (int64_t)xcd_block() * blockDim.x + threadIdx.x; i < in.m.N; i += stride) {
         T px = 0, py = 0, pz = 0;
-        if (PLANE) xform3(Tm, in.rd[i], px, py, pz);
+        if (PLANE) xform3(Tm, in.m.rd[i], px, py, pz);
         bool any = false;
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
-            const T dv = in.d[e];
+            const T dv = in.m.d[e];
             const bool kept = quality_kept(in, e, dv);
             if (keys) keys[e] = kept ? in.dens_ref[quality_orig(in, e)] : (T)__builtin_huge_val();
             if (!kept) continue;
@@ -58,13 +58,13 @@ __global__ __launch_bounds__(256) void match_quality_kernel(QualityIn<T> in, Mat
             acc[L::kSqrtSum] += (double)r;
             if (PLANE) {
                 P4<T> q, n;
-                if (in.nbr) {  // (k = 1: the records in slot order)
-                    q = in.nbr[i];
-                    n = in.nbr[in.N + i];
+                if (in.m.nbr) {  // (k = 1: the records in slot order)
+                    q = in.m.nbr[i];
+                    n = in.m.nbr[in.m.N + i];
                 } else {
-                    const int64_t g = (int64_t)in.ids[e] * in.rs;
-                    q = gld(in.ref, g);
-                    n = gld(in.nrm, g);
+                    const int64_t g = (int64_t)in.m.ids[e] * in.m.rs;
+                    q = gld(in.m.pn, g);
+                    n = gld(in.m.nrm, g);
                 }
                 const T dx = px - q.x, dy = py - q.y, dz = pz - q.z;
                 const T dot = ((dx * n.x) + (dy * n.y)) + (dz * n.z);  // PointToPlane.cpp:341-345
@@ -85,14 +85,14 @@ template <typename T, bool PLANE>
 __global__ __launch_bounds__(256) void match_overlap_kernel(QualityIn<T> in, int branch, T base,
                                                             double* __restrict__ partials) {
     double acc[1] = {0.0};
-    const int k = in.k;
+    const int k = in.m.k;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)xcd_block() * blockDim.x + threadIdx.x; i < in.N; i += stride) {
+    for (int64_t i = (int64_t)xcd_block() * blockDim.x + threadIdx.x; i < in.m.N; i += stride) {
         const T nr = branch != kQBReference ? in.noise_rd[i] : (T)0;
         bool hit = false;
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
-            const T dv = in.d[e];
+            const T dv = in.m.d[e];
             if (!quality_kept(in, e, dv)) continue;
             const T r = sqrt_rn(dv);
             if (PLANE) {

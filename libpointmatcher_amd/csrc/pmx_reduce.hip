@@ -25,31 +25,28 @@
 
 namespace pmx {
 
-// The chain's weight of one match when it holds a RobustOutlierFilter:
-// (predicates' 0/1) * robust(e^2), e^2 = dist / scale^2 in T
-// (OutlierFiltersImpl.cpp:537-540); dist = the match distance, or for
-// distanceType point2plane (n^ . (p - q))^2 with the normalised reference
-// normal (computePointToPlaneDistance, :460-489: 0 for an invalid match)
-template <typename T>
-__device__ __forceinline__ T robust_chain_weight(const WChain<T>& c, const WRange<T>& wr, T dist, int64_t e) {
-    if (c.w_arr) return c.w_arr[e];
-    const T pred = chain_keep(wr, dist) ? (T)1 : (T)0;
-    const T s = (T)*c.rb_scale;
-    const T e2 = dist / (s * s);
-    return pred * robust_weight<T>(c.rb_fct, c.rb_k, c.rb_sqa, e2);
-}
-
-// The chain's weight of entry e (slot i) in the point-to-point reductions.
-// SN (the chain holds the SurfaceNormalOutlierFilter): times the filter's 0/1,
-// which gathers the matched reference normal (these kernels carry none
-// otherwise); materialised weights (w_arr) hold the factor already.
+// The chain's weight of entry e (slot i, step point p) in the point-to-point
+// reductions: entry_weight (pmx_weight.h) with the matched normal gathered
+// only where the SurfaceNormal factor needs it (these kernels carry none
+// otherwise).  A robust point-to-plane distance is not evaluated here: its
+// weights come materialised (w_arr, every factor in them).
 template <typename T, bool SN>
-__device__ __forceinline__ T pair_weight(const WChain<T>& chain, const SNPred<T>& sn, const WRange<T>& wr,
-                                         const Mat4<T>& Tm, T dv, int64_t i, int64_t e,
-                                         const int32_t* __restrict__ ids) {
-    T w = chain.robust ? robust_chain_weight(chain, wr, dv, e) : (chain_keep(wr, dv) ? (T)1 : (T)0);
-    if (SN && !chain.w_arr && w != (T)0) w = w * (sn_entry(sn, Tm, i, ids[e]) ? (T)1 : (T)0);
-    return w;
+__device__ __forceinline__ T p2point_weight(const WChain<T>& chain, const SNPred<T>& sn, const WRange<T>& wr,
+                                            const Mat4<T>& Tm, T dv, const T (&p)[3], int64_t i, int64_t e,
+                                            const int32_t* __restrict__ ids) {
+    const auto inline_weight = [&]() {
+        const int32_t id = SN ? ids[e] : 0;
+        return entry_weight<T, SN, false>(
+            chain, sn, wr, Tm, dv, id, p[0], p[1], p[2], P4<T>{}, [&]() { return gld(sn.nrm, (int64_t)id * sn.rs); },
+            [&]() { return gld(sn.rn, i); });
+    };
+    // (the test of the array sits inside the robust side, where it was when the
+    // SN = false kernels were tuned: they compile to the same instructions)
+    const auto robust_side = [&]() {
+        if (chain.w_arr) return chain.w_arr[e];
+        return inline_weight();
+    };
+    return chain.robust ? robust_side() : inline_weight();
 }
 
 // (values: P2PlaneSums<DIM, false>, pmx_sums.h)
@@ -73,7 +70,7 @@ __global__ __launch_bounds__(256) void p2plane_partial_kernel(const P4<T>* __res
     }
     if (vzero && blockIdx.x == 0)  // (the spread counters the merged counter phase read, for the next match)
         for (int c = 0; c < 4; ++c) vzero[(size_t)(c * kVSlots + threadIdx.x) * kVStride] = 0ull;
-    p2plane_body<T, DIM, false, SN>(rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, nbr);
+    p2plane_body<T, DIM, SN>(rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, nbr);
 }
 
 // Real-valued weights (a RobustOutlierFilter in the chain; per-module path):
@@ -147,12 +144,8 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
                 q = gld(ref, (int64_t)id * rs);
                 n = gld(nrm, (int64_t)id * rs);
             }
-            const T dist = chain.rb_p2pl ? (id >= 0 ? p2pl_distance(px, py, pz, q, n) : (T)0) : dv;
-            // (the predicates judge the match distance; the robust function the chosen one)
-            const T pred = chain_keep(wr, dv) ? (T)1 : (T)0;
-            const T sc = (T)*chain.rb_scale;
-            T w = pred * robust_weight<T>(chain.rb_fct, chain.rb_k, chain.rb_sqa, dist / (sc * sc));
-            if (SN) w = w * (id >= 0 && sn_pass(chain.sn, Tm, gld(chain.sn.rn, i), n) ? (T)1 : (T)0);
+            const T w = entry_weight<T, SN>(chain, chain.sn, wr, Tm, dv, id, px, py, pz, q, loaded(n),
+                                            [&]() { return gld(chain.sn.rn, i); });
             if (!count_entry<L::kStats>(acc, w != (T)0, dv != inf)) continue;
             exist = true;
             acc[L::kStats + kSumW] += (double)w;
@@ -164,22 +157,22 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
 }
 
 template <typename T>
-void launch_p2plane_partial(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const P4<T>* nrm, int rs,
-                            const T* d, const int32_t* ids, const WChain<T>& chain, int k, int64_t N, int dim,
+void launch_p2plane_partial(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, int dim,
                             double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, unsigned long long* vzero,
-                            hipStream_t s, const P4<T>* nbr) {
+                            hipStream_t s) {
     const bool sn = chain.sn.rn != nullptr;  // (the instantiations with the normal predicate)
-    if (chain.robust) {  // real-valued weights: the full asymmetric A
+    if (chain.robust) {  // real-valued weights: the full asymmetric A (this kernel has no neighbour-record path)
         auto* const kern = dim == 3 ? (sn ? p2plane_weighted_kernel<T, 3, true> : p2plane_weighted_kernel<T, 3, false>)
                                     : (sn ? p2plane_weighted_kernel<T, 2, true> : p2plane_weighted_kernel<T, 2, false>);
-        hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials,
-                           ctl, gd);
+        hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k,
+                           m.N, partials, ctl, gd);
         return;
     }
+    // (m.nbr, k = 1: the kernel reads the records in slot order instead of gathering by id)
     auto* const kern = dim == 3 ? (sn ? p2plane_partial_kernel<T, 3, true> : p2plane_partial_kernel<T, 3, false>)
                                 : (sn ? p2plane_partial_kernel<T, 2, true> : p2plane_partial_kernel<T, 2, false>);
-    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, ctl,
-                       gd, vzero, nbr);
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k, m.N,
+                       partials, ctl, gd, vzero, m.nbr);
 }
 
 // Sum the per-block partials: one block per accumulator, each thread adds a
@@ -244,7 +237,7 @@ __device__ __forceinline__ void p2point_sums_body(const P4<T>* __restrict__ rd, 
             const int64_t e = i * k + s;
             const T dv = d[e];
             // 0/1 weights, or a robust chain's real weight (point2point distance)
-            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
+            const T w = p2point_weight<T, SN>(chain, sn, wr, Tm, dv, p, i, e, ids);
             if (!count_entry<L::kStats>(acc, w != (T)0, dv != inf)) continue;
             exist = true;
             const P4<T> q = gld(ref, ids[e]);
@@ -276,11 +269,11 @@ __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restr
 }
 
 template <typename T>
-void launch_p2point_pass1(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
-                          const WChain<T>& chain, int k, int64_t N, double* partials, const LoopCtl* ctl,
-                          const GridDesc<T>* gd, hipStream_t s) {
+void launch_p2point_pass1(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, double* partials,
+                          const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s) {
     auto* const kern = chain.sn.rn ? p2point_pass1_kernel<T, true> : p2point_pass1_kernel<T, false>;
-    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N, partials, ctl, gd);
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.ref, m.d, m.ids, chain, m.k, m.N, partials,
+                       ctl, gd);
 }
 
 // means in T: w_sum_inv = 1 / w.sum(); mean = sum * w_sum_inv (PointToPoint.cpp:67-72)
@@ -331,7 +324,7 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
             const T dv = d[e];
-            const T w = pair_weight<T, SN>(chain, sn, wr, Tm, dv, i, e, ids);
+            const T w = p2point_weight<T, SN>(chain, sn, wr, Tm, dv, p, i, e, ids);
             if (dv == inf || w == (T)0) continue;
             const P4<T> q4 = gld(ref, ids[e]);
             const T q[3] = {q4.x, q4.y, q4.z};
@@ -354,13 +347,13 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
 }
 
 template <typename T>
-void launch_p2point_pass2(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
-                          const WChain<T>& chain, int k, int64_t N, const T* means_dev, double* partials,
-                          const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s, bool similarity) {
+void launch_p2point_pass2(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, const T* means_dev,
+                          bool similarity, double* partials, const LoopCtl* ctl, const GridDesc<T>* gd,
+                          hipStream_t s) {
     auto* const kern = similarity ? (chain.sn.rn ? p2point_pass2_kernel<T, true, true> : p2point_pass2_kernel<T, false, true>)
                                   : (chain.sn.rn ? p2point_pass2_kernel<T, true, false> : p2point_pass2_kernel<T, false, false>);
-    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N, means_dev, partials,
-                       ctl, gd);
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.ref, m.d, m.ids, chain, m.k, m.N, means_dev,
+                       partials, ctl, gd);
 }
 
 // Point-to-point in one pass (device loop): the sums both of the reference's
@@ -383,68 +376,68 @@ __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __res
 }
 
 template <typename T>
-void launch_p2point_moments(const P4<T>* rd, const Mat4<T>& Tm, const P4<T>* ref, const T* d, const int32_t* ids,
-                            const WChain<T>& chain, int k, int64_t N, double* partials, const LoopCtl* ctl,
-                            const GridDesc<T>* gd, hipStream_t s) {
+void launch_p2point_moments(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, double* partials,
+                            const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s) {
     auto* const kern = chain.sn.rn ? p2point_moments_kernel<T, true> : p2point_moments_kernel<T, false>;
-    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, rd, Tm, ref, d, ids, chain, k, N, partials, ctl, gd);
+    hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.ref, m.d, m.ids, chain, m.k, m.N, partials,
+                       ctl, gd);
 }
 
-// materialise the chain's weights (host mirror only); point-to-plane robust
-// distances need the step reading, the match ids and the reference records
-template <typename T>
-__global__ void weights_chain_kernel(const T* __restrict__ d, T* __restrict__ w, int64_t n, WChain<T> chain,
-                                     const P4<T>* __restrict__ rd, Mat4<T> Tm, const P4<T>* __restrict__ ref,
-                                     const P4<T>* __restrict__ nrm, int rs, const int32_t* __restrict__ ids, int k) {
+// Materialise the chain's weight of every entry e = slot * k + rank (the host
+// mirror and what reads it; never on the hot path): entry_weight with what
+// this chain's factors need loaded first.  A robust point-to-plane distance
+// needs the step reading and the matched point and normal; the SurfaceNormal
+// factor the matched normal, which at k = 1 comes from the match's neighbour
+// record when there is one (nbr_n, slot order, no dependent gather).
+template <typename T, bool SN>
+__global__ __launch_bounds__(256) void weights_chain_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
+                                                            const P4<T>* __restrict__ ref,
+                                                            const P4<T>* __restrict__ nrm, int rs,
+                                                            const T* __restrict__ d, const int32_t* __restrict__ ids,
+                                                            WChain<T> chain, int k, int64_t n,
+                                                            const P4<T>* __restrict__ nbr_n, T* __restrict__ w) {
     const WRange<T> wr = chain_resolve(chain);
+    const bool p2pl = chain.robust && chain.rb_p2pl;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (!chain.robust) {
-            w[i] = chain_keep(wr, d[i]) ? (T)1 : (T)0;
-            continue;
-        }
-        T dist = d[i];
-        if (chain.rb_p2pl) {
-            const int32_t id = ids[i];
-            dist = 0;
-            if (id >= 0) {
-                T px, py, pz;
-                xform3(Tm, rd[i / k], px, py, pz);
-                dist = p2pl_distance(px, py, pz, gld(ref, (int64_t)id * rs), gld(nrm, (int64_t)id * rs));
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+        const int64_t i = k == 1 ? e : e / k;
+        const int32_t id = SN || p2pl ? ids[e] : -1;
+        T px = 0, py = 0, pz = 0;
+        P4<T> q{}, qn{};
+        if (id >= 0) {
+            const int64_t g = (int64_t)id * rs;
+            qn = nbr_n ? gld(nbr_n, i) : gld(nrm, g);
+            if (p2pl) {
+                q = gld(ref, g);
+                xform3(Tm, rd[i], px, py, pz);
             }
         }
-        const T pred = chain_keep(wr, d[i]) ? (T)1 : (T)0;
-        const T sc = (T)*chain.rb_scale;
-        w[i] = pred * robust_weight<T>(chain.rb_fct, chain.rb_k, chain.rb_sqa, dist / (sc * sc));
+        w[e] = entry_weight<T, SN>(chain, chain.sn, wr, Tm, d[e], id, px, py, pz, q, loaded(qn),
+                                   [&]() { return gld(chain.sn.rn, i); });
     }
 }
 template <typename T>
-void launch_weights_chain(const T* d, T* w, int64_t n, const WChain<T>& chain, const P4<T>* rd, const Mat4<T>& Tm,
-                          const P4<T>* ref, const P4<T>* nrm, int rs, const int32_t* ids, int k, hipStream_t s) {
+void launch_weights_chain(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, T* w, hipStream_t s) {
+    const int64_t n = m.N * m.k;
     if (n <= 0) return;
     int64_t g = (n + 1023) / 1024;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(weights_chain_kernel<T>, dim3((unsigned)g), dim3(256), 0, s, d, w, n, chain, rd, Tm, ref, nrm,
-                       rs, ids, k);
+    auto* const kern = chain.sn.rn ? weights_chain_kernel<T, true> : weights_chain_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k, n,
+                       m.nbr ? m.nbr + m.N : nullptr, w);
 }
 
-#define PMX_INST(T)                                                                                                  \
-    template void launch_p2plane_partial<T>(const P4<T>*, const Mat4<T>&, const P4<T>*, const P4<T>*, int, const T*, \
-                                            const int32_t*, const WChain<T>&, int, int64_t, int, double*,           \
-                                            const LoopCtl*, const GridDesc<T>*, unsigned long long*, hipStream_t,     \
-                                            const P4<T>*);                                                            \
-    template void launch_p2point_pass1<T>(const P4<T>*, const Mat4<T>&, const P4<T>*, const T*, const int32_t*,     \
-                                          const WChain<T>&, int, int64_t, double*, const LoopCtl*,                   \
-                                          const GridDesc<T>*, hipStream_t);                                          \
-    template void launch_p2point_means<T>(const double*, T*, int, const LoopCtl*, hipStream_t);                      \
-    template void launch_p2point_moments<T>(const P4<T>*, const Mat4<T>&, const P4<T>*, const T*, const int32_t*,   \
-                                            const WChain<T>&, int, int64_t, double*, const LoopCtl*,              \
-                                            const GridDesc<T>*, hipStream_t);                                      \
-    template void launch_p2point_pass2<T>(const P4<T>*, const Mat4<T>&, const P4<T>*, const T*, const int32_t*,     \
-                                          const WChain<T>&, int, int64_t, const T*, double*, const LoopCtl*,         \
-                                          const GridDesc<T>*, hipStream_t, bool);                                    \
-    template void launch_weights_chain<T>(const T*, T*, int64_t, const WChain<T>&, const P4<T>*, const Mat4<T>&,     \
-                                          const P4<T>*, const P4<T>*, int, const int32_t*, int, hipStream_t);
+#define PMX_INST(T)                                                                                                \
+    template void launch_p2plane_partial<T>(const MatchView<T>&, const Mat4<T>&, const WChain<T>&, int, double*,  \
+                                            const LoopCtl*, const GridDesc<T>*, unsigned long long*, hipStream_t); \
+    template void launch_p2point_pass1<T>(const MatchView<T>&, const Mat4<T>&, const WChain<T>&, double*,         \
+                                          const LoopCtl*, const GridDesc<T>*, hipStream_t);                        \
+    template void launch_p2point_means<T>(const double*, T*, int, const LoopCtl*, hipStream_t);                    \
+    template void launch_p2point_moments<T>(const MatchView<T>&, const Mat4<T>&, const WChain<T>&, double*,       \
+                                            const LoopCtl*, const GridDesc<T>*, hipStream_t);                      \
+    template void launch_p2point_pass2<T>(const MatchView<T>&, const Mat4<T>&, const WChain<T>&, const T*, bool,  \
+                                          double*, const LoopCtl*, const GridDesc<T>*, hipStream_t);               \
+    template void launch_weights_chain<T>(const MatchView<T>&, const Mat4<T>&, const WChain<T>&, T*, hipStream_t);
 PMX_INST(float)
 PMX_INST(double)
 #undef PMX_INST

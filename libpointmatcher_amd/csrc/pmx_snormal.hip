@@ -1,11 +1,9 @@
 // pmx_snormal.hip — SurfaceNormalOutlierFilter (pointmatcher/
 // OutlierFiltersImpl.cpp:225-285) on the device: the reading's normals made
-// resident (pmx_set_reading_normals) and the filter's weights on the module
-// path (pmx_outlier_surface_normal, materialised for the host mirror).  The
-// reductions evaluate the same predicate inline (pmx_snormal.h,
-// pmx_reduce.hip).
+// resident (pmx_set_reading_normals).  The predicate itself is sn_pass
+// (pmx_weight.h), evaluated inside the chain's weight by the reductions and
+// the materialising kernel (pmx_reduce.hip).
 #include "pmx_internal.h"
-#include "pmx_snormal.h"
 
 namespace pmx {
 
@@ -43,43 +41,9 @@ void launch_reading_normals(const T* raw, int D, const int32_t* order, int64_t n
                        n, M0, out);
 }
 
-// The filter's factor of the materialised weights: one thread per match
-// entry e = slot * k + rank, w[e] *= 0/1.  The reading normal is one
-// dwordx4 (f32) record per entry; the reference normal comes from the match's
-// neighbour record (nbr_n: k = 1, slot order, no dependent gather) or from
-// the records the ids index.  16 B reading normal + 4 B id + 16 B reference
-// normal + 8 B weight per entry (f32).
-template <typename T>
-__global__ __launch_bounds__(256) void sn_weights_kernel(T* __restrict__ w, int64_t n, int k, SNPred<T> p, Mat4<T> Tm,
-                                                         const int32_t* __restrict__ ids,
-                                                         const P4<T>* __restrict__ nbr_n) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int64_t i = k == 1 ? e : e / k;
-    const int32_t id = ids[e];
-    bool keep = false;
-    if (id >= 0) {
-        const P4<T> qn = nbr_n ? gld(nbr_n, i) : gld(p.nrm, (int64_t)id * p.rs);
-        keep = sn_pass(p, Tm, gld(p.rn, i), qn);
-    }
-    w[e] = w[e] * (keep ? (T)1 : (T)0);
-}
-
-template <typename T>
-void launch_sn_weights(T* w, int64_t n, int k, const SNPred<T>& p, const Mat4<T>& Tm, const int32_t* ids,
-                       const P4<T>* nbr_n, hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(sn_weights_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, n, k, p, Tm, ids,
-                       nbr_n);
-}
-
-#define PMX_INST(T)                                                                                              \
-    template void launch_reading_normals<T>(const T*, int, const int32_t*, int64_t, const Mat4<T>&, P4<T>*,     \
-                                            hipStream_t);                                                        \
-    template void launch_sn_weights<T>(T*, int64_t, int, const SNPred<T>&, const Mat4<T>&, const int32_t*,      \
-                                       const P4<T>*, hipStream_t);
-PMX_INST(float)
-PMX_INST(double)
-#undef PMX_INST
+template void launch_reading_normals<float>(const float*, int, const int32_t*, int64_t, const Mat4<float>&, P4<float>*,
+                                            hipStream_t);
+template void launch_reading_normals<double>(const double*, int, const int32_t*, int64_t, const Mat4<double>&,
+                                             P4<double>*, hipStream_t);
 
 }  // namespace pmx

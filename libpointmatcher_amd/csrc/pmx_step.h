@@ -1,5 +1,5 @@
 // pmx_step.h — the device form of the host's per-iteration work after the
-// minimiser (pmx_loop.hip's step kernel and pmx_post.hip's fused launch):
+// minimiser (pmx_loop.hip's step kernel):
 //   * quantile / empty-match errors of the iteration (ConvergenceError),
 //   * PointToPlane: solvePossiblyUnderdetermined on the 6x6 / 3x3 system and
 //     the rigid step (PointToPlane.cpp:108-161, 245-312); PointToPoint: the
