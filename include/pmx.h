@@ -278,6 +278,27 @@ int pmx_robust_scale(pmx_ctx* ctx, int chain_pos, double* scale);
  * PMX_E_EMPTY_QUANTILE if a quantile filter of this iteration had no finite
  * distance, PMX_E_NO_POINTS if no weight is non-zero. */
 int pmx_p2plane_system(pmx_ctx* ctx, double* A, double* b, pmx_stats* st);
+/* PointToPlaneErrorMinimizer's force2D / force4DOF (PointToPlane.cpp:177-312)
+ * for the same match: the normal equations of the forced minimisation, A
+ * n x n row-major and b as above.
+ *   PMX_FORCE_NONE  pmx_p2plane_system.
+ *   PMX_FORCE_2D    n = 3, x = (angle, t_x, t_y): the 2-D form over the x, y
+ *                   rows of the transformed reading point, the matched point
+ *                   and its normal, F = [p_x n_y - p_y n_x; n_x; n_y] and
+ *                   dot = (p_x - q_x) n_x + (p_y - q_y) n_y, without a z term:
+ *                   sums of their own, not a block of the 6-DOF ones.  On a 2-D
+ *                   context it is pmx_p2plane_system.
+ *   PMX_FORCE_4DOF  n = 4, x = (yaw, t_x, t_y, t_z): F = [p_x n_y - p_y n_x; n]
+ *                   with the full 3-D dot, which is rows and columns 2..5 of
+ *                   the 6-DOF system, bit for bit.  PMX_E_BAD_PARAM on a 2-D
+ *                   context (a dimension mismatch in the reference).
+ * The outlier chain, its weights and the statistics are the unforced ones.
+ * The step is solvePossiblyUnderdeterminedLinearSystem on (A, b), then
+ * AngleAxis(yaw, unitZ) + t (4-DOF) or the identity with Rotation2D and
+ * (t_x, t_y) in its top rows (2-D); common/pmx_dense.h holds both.  Several
+ * ranks: one all-reduce of the packed sums, as the unforced call. */
+enum { PMX_FORCE_NONE = 0, PMX_FORCE_2D = 1, PMX_FORCE_4DOF = 2 };
+int pmx_p2plane_system_forced(pmx_ctx* ctx, int force, double* A, double* b, pmx_stats* st);
 /* Point-to-point: mean_p, mean_q (D each, T values), m = sum (qc w) pc^T
  * (D x D row-major, double sums of T products). */
 int pmx_p2point_system(pmx_ctx* ctx, double* mean_p, double* mean_q, double* m, pmx_stats* st);
@@ -394,9 +415,10 @@ int pmx_sync(pmx_ctx* ctx);
  * among default / Null / MaxDist / MinDist / MedianDist / TrimmedDist /
  * VarTrimmedDist / Robust (at most one; with PointToPoint only its
  * point2point distance) / SurfaceNormal (at most one; filter_p[i][0] = eps
- * = cos(maxAngle) in T), PointToPlane (no force2D / force4DOF), with or
- * without the covariance, or PointToPoint, checkers among Counter / Differential (smoothLength < 64) /
- * Bound.  Otherwise pmx_loop_begin returns PMX_E_BAD_PARAM and the caller
+ * = cos(maxAngle) in T), PointToPlane (with force2D or force4DOF: cfg.force;
+ * 4-DOF on 3-D clouds only) or PointToPlane with the covariance (no force), or
+ * PointToPoint / PointToPointSimilarity (no force), checkers among Counter /
+ * Differential (smoothLength < 64) / Bound.  Otherwise pmx_loop_begin returns PMX_E_BAD_PARAM and the caller
  * keeps the per-module calls. */
 enum { PMX_CHECK_COUNTER = 0, PMX_CHECK_DIFFERENTIAL = 1, PMX_CHECK_BOUND = 2 };
 enum { PMX_FILTER_DEFAULT = 0, PMX_FILTER_NULL = 1, PMX_FILTER_MAXDIST = 2, PMX_FILTER_MINDIST = 3,
@@ -431,6 +453,7 @@ typedef struct pmx_loop_cfg {
     double robust_tuning;       /* after berg's tuning substitution (:419-433) */
     double robust_approx;       /* approximation (inf: none) */
     double robust_berg_target;  /* berg: the target scale */
+    int force;                  /* PMX_FORCE_* of PointToPlane (minimizer 0 only); 0: none */
 } pmx_loop_cfg;
 typedef struct pmx_loop_status {
     int iterations;             /* iterations completed (IterationsCount) */

@@ -35,6 +35,7 @@ enum {
     PMX_ICP_INVALID_ELEMENT = -5,     /* InvalidElement (unknown module name) */
     PMX_ICP_INVALID_MODULE_TYPE = -6, /* ICPChainBase::InvalidModuleType */
     PMX_ICP_CONFIGURATION_ERROR = -7, /* ConfigurationError / YAML syntax */
+    PMX_ICP_INVALID_FIELD = -8,       /* DataPoints::InvalidField (a data filter's missing descriptor) */
     PMX_ICP_RUNTIME_ERROR = -10       /* std::runtime_error (incl. HIP/RCCL failures) */
 };
 

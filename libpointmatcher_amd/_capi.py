@@ -73,7 +73,9 @@ class LoopCfg(C.Structure):
                 # PMX_FILTER_ROBUST (include/pmx.h)
                 ("robust_fct", C.c_int), ("robust_estimator", C.c_int), ("robust_p2pl", C.c_int),
                 ("robust_nb_iter_for_scale", C.c_int), ("robust_first_call", C.c_int),
-                ("robust_tuning", C.c_double), ("robust_approx", C.c_double), ("robust_berg_target", C.c_double)]
+                ("robust_tuning", C.c_double), ("robust_approx", C.c_double), ("robust_berg_target", C.c_double),
+                # PMX_FORCE_* of PointToPlane
+                ("force", C.c_int)]
 
 
 class LoopStatus(C.Structure):
@@ -152,6 +154,8 @@ class Quality(C.Structure):
                 ("links", C.c_int64), ("dist_sum", C.c_double), ("median_density", C.c_double), ("branch", C.c_int)]
 
 
+FORCE_KIND = {None: 0, "none": 0, "2D": 1, "4DOF": 2}  # PMX_FORCE_*
+
 MINIMIZER_KIND = {"PointToPlaneErrorMinimizer": 0, "PointToPointErrorMinimizer": 1,
                   "PointToPlaneWithCovErrorMinimizer": 2, "PointToPointSimilarityErrorMinimizer": 3}
 
@@ -163,7 +167,7 @@ EXPORTS = [
     "pmx_outlier_default", "pmx_outlier_null", "pmx_outlier_maxdist", "pmx_outlier_mindist",
     "pmx_outlier_mediandist", "pmx_outlier_trimmed", "pmx_outlier_vartrimmed", "pmx_outlier_robust",
     "pmx_robust_scale", "pmx_set_reading_radii", "pmx_set_reading_normals", "pmx_outlier_surface_normal",
-    "pmx_p2plane_system", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
+    "pmx_p2plane_system", "pmx_p2plane_system_forced", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid",
@@ -208,6 +212,7 @@ def lib():
         l.pmx_set_reading_normals.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_outlier_surface_normal.argtypes = [C.c_void_p, C.c_int, C.c_double]
         l.pmx_p2plane_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        l.pmx_p2plane_system_forced.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         l.pmx_p2point_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(Stats)]
         l.pmx_p2point_similarity_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -534,6 +539,17 @@ class Context:
         self._chk(self._l.pmx_p2plane_system(self.h, _ptr(A), _ptr(b), C.byref(st)))
         return A.reshape(n, n), b, st
 
+    def p2plane_system_forced(self, force):
+        """PointToPlane's force2D ("2D") / force4DOF ("4DOF") normal equations for
+        the last match (pmx_p2plane_system_forced): (A, b, stats), A 3 x 3 / 4 x 4."""
+        f = FORCE_KIND[force]
+        n = 4 if f == 2 else 3 if f == 1 or self.rows == 3 else 6
+        A = np.zeros(n * n)
+        b = np.zeros(n)
+        st = Stats()
+        self._chk(self._l.pmx_p2plane_system_forced(self.h, f, _ptr(A), _ptr(b), C.byref(st)))
+        return A.reshape(n, n), b, st
+
     def p2point_system(self):
         D = self.rows - 1
         mp = np.zeros(D)
@@ -639,7 +655,7 @@ class Context:
 
     # --- device-resident loop
     def loop_begin(self, knn=1, max_dist=np.inf, filters=(), minimizer="PointToPlaneErrorMinimizer",
-                   checkers=(), T0=None, keep_trace=False):
+                   checkers=(), T0=None, keep_trace=False, force=None):
         """filters: [(name, params...)], checkers: [(name, params...)] in chain order
         (Counter: max; Differential: rot, trans, smoothLength; Bound: rot, trans)."""
         cfg = LoopCfg()
@@ -659,6 +675,7 @@ class Context:
             for j, v in enumerate(p):
                 cfg.checker_p[i][j] = float(v)
         cfg.keep_trace = 1 if keep_trace else 0
+        cfg.force = FORCE_KIND[force]
         T0 = self._arr(np.eye(self.rows) if T0 is None else T0)
         self._loop_keep = cfg
         self._chk(self._l.pmx_loop_begin(self.h, C.byref(cfg), _ptr(T0)))

@@ -589,6 +589,39 @@ PMX_HD void p2plane_transform(int rows, const T* x, T* out) {
     }
 }
 
+// PointToPlane force4DOF (3-D): x = (yaw, t_x, t_y, t_z) -> AngleAxis(yaw, unitZ)
+// + t, with the NaN -> identity guard of the 6-DOF branch (PointToPlane.cpp:
+// 264-292).  Rows and columns 2 of the rotation are exactly those of the
+// identity while (1 - cos) + cos rounds to 1 (|yaw| <= pi / 3).
+template <typename T>
+PMX_HD void p2plane_transform_4dof(const T* x, T* out) {
+    const T axis[3] = {(T)0, (T)0, (T)1};
+    T R[9];
+    angle_axis(x[0], axis, R);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) out[r * 4 + c] = R[r * 3 + c];
+        out[r * 4 + 3] = x[1 + r];
+        out[12 + r] = 0;
+    }
+    out[15] = 1;
+    bool nan = false;
+    for (int i = 0; i < 16; ++i)
+        if (out[i] != out[i]) nan = true;
+    if (nan)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) out[r * 4 + c] = r == c ? (T)1 : (T)0;
+}
+
+// PointToPlane force2D on a 3-D cloud: x = (angle, t_x, t_y) -> the identity
+// with Rotation2D in the top-left 2 x 2 and the translation in the top-right
+// 2 x 1 (PointToPlane.cpp:296-305); no NaN guard on this branch.
+template <typename T>
+PMX_HD void p2plane_transform_force2d(const T* x, T* out) {
+    const T s = sin(x[0]), c = cos(x[0]);
+    const T m[16] = {c, -s, 0, x[1], s, c, 0, x[2], 0, 0, 1, 0, 0, 0, 0, 1};
+    for (int i = 0; i < 16; ++i) out[i] = m[i];
+}
+
 // PointToPoint: R = U V^T (reflection fixed on the last column of V),
 // t = mean_q - R mean_p, from the D x D cross-covariance m (PointToPoint.cpp:61-101)
 template <typename T>

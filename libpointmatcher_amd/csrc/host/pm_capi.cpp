@@ -42,6 +42,9 @@ int guarded(pmx_icp* icp, F&& fn) {
     } catch (const InvalidElement& e) {
         icp->err = e.what();
         return PMX_ICP_INVALID_ELEMENT;
+    } catch (const InvalidField& e) {
+        icp->err = e.what();
+        return PMX_ICP_INVALID_FIELD;
     } catch (const InvalidModuleType& e) {
         icp->err = e.what();
         return PMX_ICP_INVALID_MODULE_TYPE;

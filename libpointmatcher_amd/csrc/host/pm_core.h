@@ -42,6 +42,9 @@ struct InvalidParameter : std::runtime_error {
 struct InvalidElement : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
+struct InvalidField : std::runtime_error {  // (PointMatcher.h:213-216: a missing or mismatched descriptor)
+    using std::runtime_error::runtime_error;
+};
 struct InvalidModuleType : std::runtime_error {
     using std::runtime_error::runtime_error;
 };

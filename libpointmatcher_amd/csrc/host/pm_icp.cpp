@@ -477,26 +477,43 @@ struct PointToPlaneEM : PM<T>::ErrorMinimizer {
         if (force2D && force4DOF)
             throw ConfigurationError("Force 2D cannot be used together with force4DOF.");
     }
+    // PMX_FORCE_* of the parameters (PointToPlane.cpp:177-210)
+    int force() const { return force2D ? PMX_FORCE_2D : force4DOF ? PMX_FORCE_4DOF : PMX_FORCE_NONE; }
+    // (a derived minimiser whose estimate has no forced form refuses the flags here)
+    virtual void checkForce() const {}
     std::vector<T> compute(Device& d, int rows) override {
-        if (force2D || force4DOF)
-            throw ConfigurationError("PointToPlaneErrorMinimizer: force2D / force4DOF are outside the GPU path");
-        const int n = rows == 4 ? 6 : 3;
+        checkForce();
+        // (a dimension mismatch in the reference: an Eigen assertion)
+        if (force4DOF && rows != 4)
+            throw ConfigurationError("PointToPlaneErrorMinimizer: force4DOF needs a 3-D cloud");
+        // force2D on a 2-D cloud changes nothing (PointToPlane.cpp:179, 296-309)
+        const int f = rows == 4 ? force() : PMX_FORCE_NONE;
+        const int n = f == PMX_FORCE_4DOF ? 4 : f == PMX_FORCE_2D ? 3 : rows == 4 ? 6 : 3;
         double A[36], b[6];
         pmx_stats st;
-        d.check(pmx_p2plane_system(d.ctx, A, b, &st));
+        d.check(pmx_p2plane_system_forced(d.ctx, f, A, b, &st));
         this->setStats(st);
         T At[36], bt[6], x[6];
         for (int i = 0; i < n * n; ++i) At[i] = (T)A[i];
         for (int i = 0; i < n; ++i) bt[i] = (T)b[i];
         dense::solve_underdetermined(At, bt, n, x);
         std::vector<T> out;
-        build_p2plane_transform(rows, x, out);
+        if (f == PMX_FORCE_4DOF) {  // (shared with the device loop: pmx_dense.h)
+            out.assign(16, (T)0);
+            dense::p2plane_transform_4dof(x, out.data());
+        } else if (f == PMX_FORCE_2D) {
+            out.assign(16, (T)0);
+            dense::p2plane_transform_force2d(x, out.data());
+        } else {
+            build_p2plane_transform(rows, x, out);
+        }
         return out;
     }
     int qualityKind() const override { return 0; }
     bool loopConfig(pmx_loop_cfg& cfg) const override {
         cfg.minimizer = 0;
-        return !force2D && !force4DOF;
+        cfg.force = force();  // (4-DOF on a 2-D cloud: pmx_loop_begin refuses, compute() raises)
+        return true;
     }
 };
 
@@ -521,6 +538,10 @@ struct PointToPlaneWithCovEM : PointToPlaneEM<T> {
           sensorStdDev(this->template get<T>("sensorStdDev")),
           covMatrix(36, (T)0) {}
     int qualityKind() const override { return 2; }
+    void checkForce() const override {
+        if (this->force2D || this->force4DOF)
+            throw ConfigurationError("PointToPlaneWithCovErrorMinimizer: force2D / force4DOF are outside the GPU path");
+    }
     bool loopConfig(pmx_loop_cfg& cfg) const override {
         cfg.minimizer = 2;  // (PointToPlane's iterations; the step keeps the increments)
         return !this->force2D && !this->force4DOF;
@@ -982,6 +1003,81 @@ struct SimpleSensorNoiseDPF : PM<T>::DataPointsFilter {
     }
 };
 
+// ObservationDirectionDataPointsFilter (DataPointsFilters/ObservationDirection.cpp:
+// 39-88, parameters ObservationDirection.h:63-70): the descriptor
+// "observationDirections" (span D) = centre - p, the sensor centre (x, y[, z])
+// in the cloud's frame.  Host code, elementwise, once per compute, like
+// SimpleSensorNoise above; nothing in the ICP loop reads it, so it is not
+// uploaded.
+template <typename T>
+struct ObservationDirectionDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("x", "x-coordinate of sensor", "0"), PDoc("y", "y-coordinate of sensor", "0"),
+                PDoc("z", "z-coordinate of sensor", "0")};
+    }
+    const T centerX, centerY, centerZ;
+    explicit ObservationDirectionDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("ObservationDirectionDataPointsFilter", doc(), p),
+          centerX(this->template get<T>("x")),
+          centerY(this->template get<T>("y")),
+          centerZ(this->template get<T>("z")) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        const int dim = cloud.rows, D = dim - 1;
+        if (D != 2 && D != 3)
+            throw InvalidField("ObservationDirectionDataPointsFilter: Error, works only in 2 or 3 dimensions, cloud has " +
+                               std::to_string(D) + " dimensions.");
+        const T center[3] = {centerX, centerY, centerZ};
+        std::vector<T> obs((size_t)cloud.n * D);
+        const T* f = cloud.feat();
+        for (int64_t j = 0; j < cloud.n; ++j)
+            for (int r = 0; r < D; ++r) obs[(size_t)j * D + r] = center[r] - f[(size_t)j * dim + r];
+        cloud.setDescriptor("observationDirections", D, obs.data());
+    }
+};
+
+// OrientNormalsDataPointsFilter (DataPointsFilters/OrientNormals.cpp:40-92,
+// parameter OrientNormals.h:59-64): "normals" flipped where they point away
+// from (towardCenter 1: obs . n < 0) or towards (0: obs . n > 0) the sensor;
+// the dot is formed in T and compared as a double, as in the reference.  Both
+// descriptors must exist (InvalidField).  Host code, elementwise.
+template <typename T>
+struct OrientNormalsDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("towardCenter",
+                     "If true (1), every normal is turned to point toward the observation point; if false (0), away "
+                     "from it.",
+                     "1", "0", "1", &P::Comp<bool>)};
+    }
+    const bool towardCenter;
+    explicit OrientNormalsDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("OrientNormalsDataPointsFilter", doc(), p),
+          towardCenter(this->template get<bool>("towardCenter")) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        if (!cloud.descriptorExists("normals"))
+            throw InvalidField("OrientNormalsDataPointsFilter: Error, cannot find normals in descriptors.");
+        if (!cloud.descriptorExists("observationDirections"))
+            throw InvalidField(
+                "OrientNormalsDataPointsFilter: Error, cannot find observation directions in descriptors.");
+        int span = 0, ospan = 0;
+        std::vector<T> nrm = cloud.descriptor("normals", &span);
+        const std::vector<T> obs = cloud.descriptor("observationDirections", &ospan);
+        if (span != ospan)  // (an assertion in the reference)
+            throw InvalidField("OrientNormalsDataPointsFilter: normals and observationDirections differ in rows");
+        for (int64_t j = 0; j < cloud.n; ++j) {
+            T* n = &nrm[(size_t)j * span];
+            const T* o = &obs[(size_t)j * span];
+            T s = o[0] * n[0];  // (Eigen's dot: sequential in T)
+            for (int r = 1; r < span; ++r) s = s + o[r] * n[r];
+            const double scalar = (double)s;
+            if (towardCenter ? scalar < 0 : scalar > 0)
+                for (int r = 0; r < span; ++r) n[r] = -n[r];
+        }
+        cloud.setDescriptor("normals", span, nrm.data());
+    }
+};
+
 // DistanceLimitDataPointsFilter (DataPointsFilters/DistanceLimit.cpp:57-128,
 // DistanceLimit.h:57-63): MaxDist (removeInside 0: keep < dist) and MinDist
 // (removeInside 1: keep > dist) in one filter, on coordinate dim or the
@@ -1359,6 +1455,10 @@ PointMatcher<T>::PointMatcher() {
                                   [](const Ps& p) { return std::make_shared<DistDPF<T, false>>(p); }, true);
     DataPointsFilterRegistrar.reg("SimpleSensorNoiseDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<SimpleSensorNoiseDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("ObservationDirectionDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<ObservationDirectionDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("OrientNormalsDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<OrientNormalsDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("DistanceLimitDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<DistanceLimitDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("VoxelGridDataPointsFilter",

@@ -1517,15 +1517,17 @@ int finish_sums(pmx_ctx* c, const PendingSums& p) {
     return allreduce_f64(c, p.out, p.nv);
 }
 
-// the point-to-plane system's partials (no host sync; *last: its sum, pmx_ctx.h)
+// the point-to-plane system's partials (no host sync; *last: its sum, pmx_ctx.h);
+// force (PMX_FORCE_*): the form of the sums, p2plane_sums_dim
 template <typename T>
-int p2plane_enqueue(pmx_ctx* c, PendingSums* last) {
+int p2plane_enqueue(pmx_ctx* c, int force, PendingSums* last) {
     const WChain<T> chain = chain_of<T>(c);
-    launch_p2plane_partial<T>(match_view<T>(c), step_mat<T>(c), chain, c->dim, c->d_partials, loop_ctl(c),
+    const int form = p2plane_sums_dim(c->dim, force);
+    launch_p2plane_partial<T>(match_view<T>(c), step_mat<T>(c), chain, form, c->d_partials, loop_ctl(c),
                               (const GridDesc<T>*)c->d_gdesc, c->vpart_dirty ? c->d_vpart : nullptr, c->stream);
     c->vpart_dirty = false;
     HIPCHK(c, hipGetLastError());
-    *last = {c->d_result, p2plane_nv(c->dim, chain.robust)};
+    *last = {c->d_result, p2plane_nv(form, chain.robust)};
     return PMX_OK;
 }
 
@@ -1579,23 +1581,29 @@ int check_minimised(pmx_ctx* c, const SumStats& s) {
 }
 
 template <typename T>
-int p2plane_impl(pmx_ctx* c, double* A, double* b, pmx_stats* st) {
+int p2plane_impl(pmx_ctx* c, int force, double* A, double* b, pmx_stats* st) {
+    if (force < PMX_FORCE_NONE || force > PMX_FORCE_4DOF) return fail(c, PMX_E_BAD_PARAM, "force: not a PMX_FORCE_* value");
+    if (force == PMX_FORCE_4DOF && c->d_ref && c->dim != 3)
+        return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer: force4DOF needs a 3-D cloud");
     int rc = check_match(c);
     if (rc) return rc;
     if (!c->has_normals)
         return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer requires \"normals\" on the reference");
     const bool full = c->rb_pos >= 0 && c->rb_pos < c->chain_n;  // (the weighted layout, see p2plane_enqueue)
     PendingSums last;
-    if ((rc = p2plane_enqueue<T>(c, &last))) return rc;
+    if ((rc = p2plane_enqueue<T>(c, force, &last))) return rc;
     if ((rc = finish_sums(c, last))) return rc;
     if ((rc = readback(c))) return rc;
     after_readback(c);
     const double* r = c->h_result;
-    const SumStats s = c->dim == 3 ? p2plane_stats<3>(r, full) : p2plane_stats<2>(r, full);
+    const int form = p2plane_sums_dim(c->dim, force);
+    const SumStats s = form == 3 ? p2plane_stats<3>(r, full) : p2plane_stats<2>(r, full);
     fill_stats(c, st, s, module_limit(c));
     if ((rc = check_minimised(c, s))) return rc;
     // (the triangle mirrored: exactly symmetric with 0/1 weights, see pmx_reduce.hip)
-    if (c->dim == 3)
+    if (force == PMX_FORCE_4DOF)
+        full ? p2plane_unpack_4dof<double, true>(r, A, b) : p2plane_unpack_4dof<double, false>(r, A, b);
+    else if (form == 3)
         full ? p2plane_unpack<double, 3, true>(r, A, b) : p2plane_unpack<double, 3, false>(r, A, b);
     else
         full ? p2plane_unpack<double, 2, true>(r, A, b) : p2plane_unpack<double, 2, false>(r, A, b);
@@ -1795,7 +1803,7 @@ int get_weights_impl(pmx_ctx* c, void* w) {
     template int match_impl<T>(pmx_ctx*, const T*, int, double, uint64_t*);                  \
     template int outlier_impl<T>(pmx_ctx*, int, int, double, double, double);               \
     template int outlier_robust_impl<T>(pmx_ctx*, int, int, double, double, int, double, int); \
-    template int p2plane_enqueue<T>(pmx_ctx*, PendingSums*);                                \
+    template int p2plane_enqueue<T>(pmx_ctx*, int, PendingSums*);                           \
     template int p2point_enqueue<T>(pmx_ctx*, bool, PendingSums*);                          \
     template int p2plane_cov_impl<T>(pmx_ctx*, const T*, double*, double*, int64_t*);       \
     template int quality_impl<T>(pmx_ctx*, const T*, int, pmx_quality*);                    \
@@ -1897,8 +1905,12 @@ int pmx_outlier_vartrimmed(pmx_ctx* c, int pos, double a, double b, double l) { 
 int pmx_outlier_surface_normal(pmx_ctx* c, int pos, double eps) { return OUTLIER(c, 8, pos, eps, 0, 0); }
 
 int pmx_p2plane_system(pmx_ctx* c, double* A, double* b, pmx_stats* st) {
+    return pmx_p2plane_system_forced(c, PMX_FORCE_NONE, A, b, st);
+}
+
+int pmx_p2plane_system_forced(pmx_ctx* c, int force, double* A, double* b, pmx_stats* st) {
     if (!c || !A || !b) return fail(c, PMX_E_BAD_PARAM, "null argument");
-    return DISPATCH(c, p2plane_impl<float>(c, A, b, st), p2plane_impl<double>(c, A, b, st));
+    return DISPATCH(c, p2plane_impl<float>(c, force, A, b, st), p2plane_impl<double>(c, force, A, b, st));
 }
 
 int pmx_p2plane_covariance(pmx_ctx* c, const void* T_step, double* H, double* Q, int64_t* pairs) {

@@ -431,7 +431,7 @@ struct PendingSums {
 };
 int finish_sums(pmx_ctx* c, const PendingSums& p);  // launch_finalize, then the ranks' sum
 template <typename T>
-int p2plane_enqueue(pmx_ctx* c, PendingSums* last);
+int p2plane_enqueue(pmx_ctx* c, int force, PendingSums* last);  // (force: PMX_FORCE_*, the sums' form)
 // similarity: PointToPointSimilarity's sums (sigma after the moments, two passes always)
 template <typename T>
 int p2point_enqueue(pmx_ctx* c, bool similarity, PendingSums* last);

@@ -32,9 +32,15 @@ struct Mat4d {
     double m[16];
 };
 
+// LoopCfg.minimizer of PointToPlane with pmx_loop_cfg.force on a 3-D context:
+// the step reads the forced form's sums and builds the forced transform
+enum { kStepForce2D = 3, kStepForce4DOF = 4 };
+
 struct LoopCfg {
     int rows;       // 3 (2-D) or 4 (3-D)
-    int minimizer;  // 0 point-to-plane, 1 point-to-point, 2 point-to-point similarity (pmx_loop_cfg.minimizer 3)
+    // 0 point-to-plane, 1 point-to-point, 2 point-to-point similarity
+    // (pmx_loop_cfg.minimizer 3), kStepForce2D, kStepForce4DOF
+    int minimizer;
     int full;       // point-to-plane: the weighted reduction's layout (full A; a RobustOutlierFilter chain)
     int n_checkers;
     int checker_kind[kMaxCheckers];

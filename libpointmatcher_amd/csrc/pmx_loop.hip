@@ -51,8 +51,17 @@ __device__ __forceinline__ void diag_record(long long* __restrict__ diag, const 
         LAUNCH(R, 1);            \
     else                         \
         LAUNCH(R, 2)
-#define PMX_STEP_DISPATCH(LAUNCH) \
-    if (cfg.rows == 4) { PMX_STEP_MIN(LAUNCH, 4); } else { PMX_STEP_MIN(LAUNCH, 3); }
+// (the forced point-to-plane steps exist for 3-D contexts only: loop_begin_impl)
+#define PMX_STEP_DISPATCH(LAUNCH)                                   \
+    if (cfg.rows == 4 && cfg.minimizer == kStepForce2D) {           \
+        LAUNCH(4, kStepForce2D);                                    \
+    } else if (cfg.rows == 4 && cfg.minimizer == kStepForce4DOF) {  \
+        LAUNCH(4, kStepForce4DOF);                                  \
+    } else if (cfg.rows == 4) {                                     \
+        PMX_STEP_MIN(LAUNCH, 4);                                    \
+    } else {                                                        \
+        PMX_STEP_MIN(LAUNCH, 3);                                    \
+    }
 
 // The step after the minimiser (pmx_step.h); res holds the system (one lane
 // runs it; folding the last finalize into this launch measured slower: the

@@ -77,6 +77,14 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     if (cfg->minimizer != 0 && cfg->minimizer != 1) return fail(c, PMX_E_BAD_PARAM, "device loop: unknown minimizer");
     if (cfg->minimizer == 0 && !c->has_normals)
         return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer requires \"normals\" on the reference");
+    // force2D / force4DOF (PointToPlane.cpp:177-210): PointToPlane's alone, the
+    // covariance is not estimated for them; 4-DOF is a 3-D cloud's
+    if (cfg->force < PMX_FORCE_NONE || cfg->force > PMX_FORCE_4DOF)
+        return fail(c, PMX_E_BAD_PARAM, "device loop: force is not a PMX_FORCE_* value");
+    if (cfg->force != PMX_FORCE_NONE && (cfg->minimizer != 0 || with_cov))
+        return fail(c, PMX_E_BAD_PARAM, "device loop: force2D / force4DOF need PointToPlaneErrorMinimizer (minimizer 0)");
+    if (cfg->force == PMX_FORCE_4DOF && c->dim != 3)
+        return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer: force4DOF needs a 3-D cloud");
     if (cfg->n_checkers < 0 || cfg->n_checkers > kMaxCheckers)
         return fail(c, PMX_E_BAD_PARAM, "device loop: at most 8 transformation checkers");
     for (int i = 0; i < cfg->n_checkers; ++i) {
@@ -91,6 +99,9 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     LoopCfg d{};
     d.rows = c->rows;
     d.minimizer = similarity ? 2 : cfg->minimizer;
+    // (force2D on a 2-D cloud changes nothing: the unforced step)
+    if (c->dim == 3 && cfg->force == PMX_FORCE_2D) d.minimizer = kStepForce2D;
+    if (c->dim == 3 && cfg->force == PMX_FORCE_4DOF) d.minimizer = kStepForce4DOF;
     d.full = n_robust > 0 ? 1 : 0;  // (point-to-plane: the weighted system's full A layout)
     d.n_checkers = cfg->n_checkers;
     for (int i = 0; i < cfg->n_checkers; ++i) {
@@ -282,7 +293,8 @@ int loop_enqueue_iteration(pmx_ctx* c) {
         if ((rc = outlier_impl<T>(c, cfg.filter_kind[i], i, p[0], p[1], p[2]))) return rc;
     }
     PendingSums last;
-    rc = cfg.minimizer == 0 ? p2plane_enqueue<T>(c, &last) : p2point_enqueue<T>(c, c->loop_dev.minimizer == 2, &last);
+    rc = cfg.minimizer == 0 ? p2plane_enqueue<T>(c, cfg.force, &last)
+                            : p2point_enqueue<T>(c, c->loop_dev.minimizer == 2, &last);
     const bool step_counter = c->step_counter;
     c->step_counter = false;
     if (rc) return rc;

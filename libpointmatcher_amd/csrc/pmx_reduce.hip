@@ -156,6 +156,12 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
     block_store<NV>(acc, partials);
 }
 
+// dim: the sums' form (p2plane_sums_dim, pmx_sums.h), not the context's
+// dimension.  Every instantiation transforms, loads and gathers whole 3-D
+// records (a 2-D context's z is 0) and DIM selects the accumulation alone, so
+// force2D on a 3-D context is the DIM = 2 instantiation as it stands: the 3-D
+// step transform (xform3), the 3-D records, the chain's 3-D predicates and
+// weights, and p2plane_add<T, 2> on the x, y of p, q and n.
 template <typename T>
 void launch_p2plane_partial(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, int dim,
                             double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, unsigned long long* vzero,

@@ -73,6 +73,19 @@ __device__ __noinline__ void loop_solve_rank_deficient(const double* __restrict_
     solve_rank_deficient(A, b, NF, x);
     for (int i = 0; i < NF; ++i) xout[i] = x[i];
 }
+// (force4DOF: the 4-DOF block of the 3-D form's sums, pmx_sums.h)
+template <typename T>
+__device__ __noinline__ void loop_solve_rank_deficient_4dof(const double* __restrict__ res, int full,
+                                                            T* __restrict__ xout) {
+    constexpr int NF = P2Plane4DofSums::NF;
+    T A[36], b[6], x[6];
+    if (full)
+        p2plane_unpack_4dof<T, true>(res, A, b);
+    else
+        p2plane_unpack_4dof<T, false>(res, A, b);
+    solve_rank_deficient(A, b, NF, x);
+    for (int i = 0; i < NF; ++i) xout[i] = x[i];
+}
 
 // A sufficient condition for FullPivHouseholderQR(A).isInvertible() of the
 // SPD point-to-plane system, from its LLT factor: lambda_min(A) >=
@@ -123,8 +136,9 @@ __device__ __forceinline__ bool well_conditioned(const T* A, const T* L) {
 // ROWS is the homogeneous dimension (4 in 3-D, 3 in 2-D): with every size a
 // compile-time constant the dense kit's arrays live in VGPRs, not scratch
 // (a single lane walking scratch took ~75 us per iteration at C3).
-// MIN: the minimiser (0 point-to-plane, 1 point-to-point, 2 point-to-point
-// similarity) as a template parameter, so each kernel holds one minimiser's
+// MIN: the minimiser (LoopCfg.minimizer: 0 point-to-plane, 1 point-to-point, 2
+// point-to-point similarity, 3 / 4 point-to-plane with force2D / force4DOF on a
+// 3-D context) as a template parameter, so each kernel holds one minimiser's
 // dense code (registers).
 template <typename T, int ROWS, int MIN>
 __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T>* __restrict__ S,
@@ -132,6 +146,10 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
                                        unsigned long long vis1, const T* __restrict__ means, const LoopCfg& cfg,
                                        T* __restrict__ trace) {
     constexpr int rows = ROWS, D = ROWS - 1;
+    constexpr bool kPlane = MIN == 0 || MIN == kStepForce2D || MIN == kStepForce4DOF;
+    constexpr bool kDof4 = MIN == kStepForce4DOF;
+    constexpr int SD = MIN == kStepForce2D ? 2 : D;  // the sums' form (p2plane_sums_dim)
+    static_assert(MIN <= 2 || ROWS == 4, "the forced modes are a 3-D context's");
     // Every global read of the step first, together: the data was written
     // by other XCDs' kernels, so each read is a memory round trip, and in
     // use order they were serialised (~1.5 us of the kernel, clock64
@@ -144,7 +162,7 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
 #pragma unroll
     for (int ci = 0; ci < kMaxCheckers; ++ci) cnt[ci] = S->cond[ci][0];
     // statistics of the iteration (ErrorElements, ErrorMinimizer.cpp:133-192)
-    const SumStats st = MIN == 0 ? p2plane_stats<D>(res, cfg.full != 0) : p2point_stats(res);
+    const SumStats st = kPlane ? p2plane_stats<SD>(res, cfg.full != 0) : p2point_stats(res);
     S->last_level = level_now;  // the level whose positions this iteration's ids are
     // the next match may reuse this one's output (pmx_grid.hip temporal reuse)
     for (int i = 0; i < 16; ++i) ctl->Tprev[i] = ctl->T[i];
@@ -168,14 +186,21 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
     S->touched += vis0;
     // the step transform
     T dT[16];
-    if constexpr (MIN == 0) {
-        constexpr int NF = P2PlaneSums<D, false>::NF;
+    if constexpr (kPlane) {
+        constexpr int NF = kDof4 ? P2Plane4DofSums::NF : P2PlaneSums<SD, false>::NF;
         T A[NF * NF], b[NF], x[NF], L[NF * NF];
         // (full: a robust chain, (w F_r) F_c in T, the reference's asymmetric wF * F^T)
-        if (cfg.full)
-            p2plane_unpack<T, D, true>(res, A, b);
-        else
-            p2plane_unpack<T, D, false>(res, A, b);
+        if constexpr (kDof4) {
+            if (cfg.full)
+                p2plane_unpack_4dof<T, true>(res, A, b);
+            else
+                p2plane_unpack_4dof<T, false>(res, A, b);
+        } else {
+            if (cfg.full)
+                p2plane_unpack<T, SD, true>(res, A, b);
+            else
+                p2plane_unpack<T, SD, false>(res, A, b);
+        }
         // solve_full_rank: FullPivQR(A).isInvertible() -> LLT solve.  The
         // QR's rank test is skipped when the LLT factor proves A far from
         // rank-deficient (well_conditioned below): its answer is then known.
@@ -189,10 +214,18 @@ __device__ __forceinline__ void step_body(LoopCtl* __restrict__ ctl, LoopState<T
         if (full) {
             llt_solve(L, NF, b, x);
         } else {
-            loop_solve_rank_deficient<T, D>(res, cfg.full, S->xsolve);
+            if constexpr (kDof4)
+                loop_solve_rank_deficient_4dof<T>(res, cfg.full, S->xsolve);
+            else
+                loop_solve_rank_deficient<T, SD>(res, cfg.full, S->xsolve);
             for (int i = 0; i < NF; ++i) x[i] = S->xsolve[i];
         }
-        p2plane_transform(rows, x, dT);
+        if constexpr (kDof4)
+            p2plane_transform_4dof(x, dT);
+        else if constexpr (MIN == kStepForce2D)
+            p2plane_transform_force2d(x, dT);
+        else
+            p2plane_transform(rows, x, dT);
     } else {
         using PS = P2PointSums;
         T m[9], mp[3], mq[3];

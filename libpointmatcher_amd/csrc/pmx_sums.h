@@ -38,6 +38,28 @@ constexpr int p2plane_nv(int dim, bool full) {
                     : (full ? P2PlaneSums<2, true>::NV : P2PlaneSums<2, false>::NV);
 }
 
+// PointToPlane's force2D / force4DOF (PointToPlane.cpp:177-210; the values of
+// PMX_FORCE_*, pmx.h).
+enum { kForceNone = 0, kForce2D = 1, kForce4DOF = 2 };
+// force2D on a 3-D context: the 2-D form over the x, y rows of the transformed
+// reading point, of the matched point and of its normal (dot has no z term), so
+// the sums are P2PlaneSums<2, FULL> from the 2-D accumulation run on the 3-D
+// records.  On a 2-D context it changes nothing.  This is the form (the DIM of
+// P2PlaneSums and of the reduction) a context's dimension and the force select.
+constexpr int p2plane_sums_dim(int dim, int force) { return force == kForce2D ? 2 : dim; }
+// force4DOF (3-D only): F = [p_x n_y - p_y n_x; n], the rows F[2..5] of the 3-D
+// form with the same dot, so x = (yaw, t) solves rows and columns kFirst.. of
+// P2PlaneSums<3, FULL>; nothing else is accumulated.
+struct P2Plane4DofSums {
+    static constexpr int NF = 4, kFirst = 2;
+};
+// the unknowns of the step's system
+constexpr int p2plane_nf(int dim, int force) {
+    return force == kForce4DOF                  ? P2Plane4DofSums::NF
+           : p2plane_sums_dim(dim, force) == 3 ? P2PlaneSums<3, false>::NF
+                                               : P2PlaneSums<2, false>::NF;
+}
+
 // Point-to-point.  Pass 1: sum w, sum w p, sum w q, the ErrorElements counts.
 // Two passes: the centred moments sum (w qc_r) pc_c from kPass2At, the
 // similarity minimiser's sigma behind them.  One pass (device loop, double):
@@ -76,6 +98,14 @@ static_assert(P2PlaneSums<3, true>::NV <= kNVMax && P2PlaneSums<3, false>::NV <=
 static_assert(kStepRes == 48 && P2PlaneSums<3, true>::NV <= kStepRes && P2PointSums::kMomentsNV <= kStepRes &&
                   P2PointSums::kSigma < kStepRes,
               "the step reads the first kStepRes doubles");
+static_assert(P2PlaneSums<3, true>::NV == 47 && P2PlaneSums<3, false>::NV == 32,
+              "the 3-D triangle fills a 32-value transpose (block_store): a forced mode adds nothing to it");
+static_assert(P2PlaneSums<2, true>::NV == 17 && P2PlaneSums<2, false>::NV == 14 && p2plane_sums_dim(3, kForce2D) == 2 &&
+                  p2plane_sums_dim(3, kForce4DOF) == 3 && p2plane_sums_dim(2, kForce2D) == 2,
+              "force2D reduces a 3-D context into the 2-D form");
+static_assert(P2Plane4DofSums::kFirst + P2Plane4DofSums::NF == P2PlaneSums<3, false>::NF && p2plane_nf(3, kForce4DOF) == 4 &&
+                  p2plane_nf(3, kForce2D) == 3 && p2plane_nf(3, kForceNone) == 6 && p2plane_nf(2, kForceNone) == 3,
+              "the 4-DOF system is the trailing block of the 3-D one");
 static_assert(P2PointSums::kPass1NV <= P2PointSums::kPass2At, "pass 1 ends before the second pass's sums");
 static_assert(kStepRes <= kCovAt && kCovAt + kCovNV <= kResultDoubles, "the covariance behind the step's area");
 static_assert(kCovAt + kCovNV <= QualitySums::kAt && QualitySums::kAt + QualitySums::kNV <= kResultDoubles &&
@@ -109,6 +139,30 @@ PMX_SUMS_HD void p2plane_unpack(const double* __restrict__ r, T* A, T* b) {
     }
 #pragma unroll
     for (int i = 0; i < NF; ++i) b[i] = (T)(-r[L::kB + i]);
+}
+
+// force4DOF's normal equations from the 3-D form's sums: rows and columns
+// P2Plane4DofSums::kFirst.. of p2plane_unpack<T, 3, FULL>'s A and b, the same
+// values cast the same way (moves and casts only).
+template <typename T, bool FULL>
+PMX_SUMS_HD void p2plane_unpack_4dof(const double* __restrict__ r, T* A, T* b) {
+    using L = P2PlaneSums<3, FULL>;
+    constexpr int NF = L::NF, N4 = P2Plane4DofSums::NF, K = P2Plane4DofSums::kFirst;
+    if constexpr (FULL) {
+#pragma unroll
+        for (int i = 0; i < N4; ++i)
+#pragma unroll
+            for (int j = 0; j < N4; ++j) A[i * N4 + j] = (T)r[(K + i) * NF + K + j];
+    } else {
+        int a = 0;  // (the triangle's index, walked as p2plane_unpack walks it)
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = i; j < NF; ++j, ++a)
+                if (i >= K) A[(i - K) * N4 + (j - K)] = A[(j - K) * N4 + (i - K)] = (T)r[a];
+    }
+#pragma unroll
+    for (int i = 0; i < N4; ++i) b[i] = (T)(-r[L::kB + K + i]);
 }
 
 }  // namespace pmx

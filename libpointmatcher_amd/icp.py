@@ -26,6 +26,11 @@ class InvalidElement(RuntimeError):
     """InvalidElement (pointmatcher/Registrar.h:69-72): unknown module name."""
 
 
+class InvalidField(RuntimeError):
+    """DataPoints::InvalidField (pointmatcher/PointMatcher.h:213-216): a data
+    filter did not find a descriptor it needs."""
+
+
 class InvalidModuleType(RuntimeError):
     """ICPChainBase::InvalidModuleType (pointmatcher/ICP.cpp:158-166)."""
 
@@ -35,7 +40,7 @@ class ConfigurationError(RuntimeError):
 
 
 _ERR = {-1: ConvergenceError, -3: InvalidParameter, -4: TransformationError, -5: InvalidElement,
-        -6: InvalidModuleType, -7: ConfigurationError, -10: RuntimeError}
+        -6: InvalidModuleType, -7: ConfigurationError, -8: InvalidField, -10: RuntimeError}
 
 
 class IcpStats(C.Structure):
