@@ -26,6 +26,10 @@
  *                       SurfaceNormalOutlierFilter::compute on the step reading's
  *                         rotated "normals" (OutlierFiltersImpl.cpp:225-285,
  *                          ICP.cpp:381-390)
+ *   pmx_set_reference_weight_descriptor / pmx_outlier_generic_descriptor
+ *                       GenericDescriptorOutlierFilter::compute on a one-row
+ *                         descriptor of the filtered reference
+ *                         (OutlierFiltersImpl.cpp:290-374)
  *   pmx_p2plane_system  ErrorElements + PointToPlane normal equations
  *                         (ErrorMinimizer.cpp:58-193, PointToPlane.cpp:171-243)
  *   pmx_p2point_system  ErrorElements + PointToPoint weighted moments
@@ -211,6 +215,14 @@ int pmx_set_reading_noise(pmx_ctx* ctx, const void* noise);
  * not be NaN: the median is taken from their sorted order, where a NaN would
  * rank by its bit pattern. */
 int pmx_set_reference_descriptors(pmx_ctx* ctx, const void* noise, const void* densities);
+/* GenericDescriptorOutlierFilter: the one-row descriptor of the reference that
+ * the filter reads, M T values in the order of pmx_set_reference's points.
+ * NULL clears it, and so does the next pmx_set_reference.  Every built grid
+ * level keeps a copy in its own point order, so a pair gathers its value by
+ * the match id alone.  The values must not be NaN: the soft form's maximum is
+ * taken with comparisons, which a NaN would drop or keep depending on where
+ * it stands. */
+int pmx_set_reference_weight_descriptor(pmx_ctx* ctx, const void* desc);
 
 /* ------------------------------------------------------------- match --- */
 /* search structure, mirroring KDTreeMatcher's searchType
@@ -252,6 +264,20 @@ int pmx_outlier_vartrimmed(pmx_ctx* ctx, int chain_pos, double minRatio, double 
  * filter is all ones, entries without neighbour included.  It reads no
  * distance, so the quantile filters of the same chain are unaffected. */
 int pmx_outlier_surface_normal(pmx_ctx* ctx, int chain_pos, double eps);
+/* GenericDescriptorOutlierFilter::compute (OutlierFiltersImpl.cpp:312-374) for
+ * the last pmx_match, on the descriptor of pmx_set_reference_weight_descriptor
+ * (PMX_E_STATE without one); at most one per chain (PMX_E_BAD_PARAM).  With id
+ * the matched reference point: w = 0 for an entry without neighbour; hard
+ * (soft == 0): w = desc[id] > threshold (larger_than != 0) or desc[id] <
+ * threshold, both strict and in T, 1 or 0; soft: w = desc[id] / m, a division
+ * in T, m the maximum of the undivided weights over all k x N entries of every
+ * rank, the zeros of the entries without neighbour included (m <= 0 is not
+ * guarded: IEEE gives the infinities and NaNs the reference gives).  The soft
+ * form's weights are real-valued: the systems are the weighted ones, as with
+ * the RobustOutlierFilter; a pair of weight 0 is not kept, one of negative
+ * weight is.  It reads no distance, so the quantile filters of the same
+ * chain are unaffected. */
+int pmx_outlier_generic_descriptor(pmx_ctx* ctx, int chain_pos, int soft, int larger_than, double threshold);
 /* RobustOutlierFilter::robustFiltering (OutlierFiltersImpl.cpp:494-598):
  * real-valued weights w = robust(e^2), e^2 = dist / scale^2; at most one per
  * chain.  robust_fct: PMX_RF_*; tuning: k (after the berg substitution,
@@ -415,7 +441,9 @@ int pmx_sync(pmx_ctx* ctx);
  * among default / Null / MaxDist / MinDist / MedianDist / TrimmedDist /
  * VarTrimmedDist / Robust (at most one; with PointToPoint only its
  * point2point distance) / SurfaceNormal (at most one; filter_p[i][0] = eps
- * = cos(maxAngle) in T), PointToPlane (with force2D or force4DOF: cfg.force;
+ * = cos(maxAngle) in T) / GenericDescriptor (at most one; filter_p[i] = {soft,
+ * larger_than, threshold}; needs pmx_set_reference_weight_descriptor, else
+ * PMX_E_STATE; any minimiser of the loop), PointToPlane (with force2D or force4DOF: cfg.force;
  * 4-DOF on 3-D clouds only) or PointToPlane with the covariance (no force), or
  * PointToPoint / PointToPointSimilarity (no force), checkers among Counter /
  * Differential (smoothLength < 64) / Bound.  Otherwise pmx_loop_begin returns PMX_E_BAD_PARAM and the caller
@@ -423,7 +451,7 @@ int pmx_sync(pmx_ctx* ctx);
 enum { PMX_CHECK_COUNTER = 0, PMX_CHECK_DIFFERENTIAL = 1, PMX_CHECK_BOUND = 2 };
 enum { PMX_FILTER_DEFAULT = 0, PMX_FILTER_NULL = 1, PMX_FILTER_MAXDIST = 2, PMX_FILTER_MINDIST = 3,
        PMX_FILTER_MEDIANDIST = 4, PMX_FILTER_TRIMMED = 5, PMX_FILTER_VARTRIMMED = 6, PMX_FILTER_ROBUST = 7,
-       PMX_FILTER_SURFACENORMAL = 8 };
+       PMX_FILTER_SURFACENORMAL = 8, PMX_FILTER_GENERICDESCRIPTOR = 9 };
 /* RobustOutlierFilter's scale estimator in a loop configuration */
 enum { PMX_RSE_NONE = 0, PMX_RSE_MAD = 1, PMX_RSE_STD = 2, PMX_RSE_BERG = 3 };
 typedef struct pmx_loop_cfg {

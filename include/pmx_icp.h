@@ -57,6 +57,11 @@ int pmx_icp_create(int dtype, int device, pmx_icp** out);
 void pmx_icp_destroy(pmx_icp* icp);
 const char* pmx_icp_last_error(const pmx_icp* icp);
 
+/* The parameter documentation of a registered outlier filter, one line per
+ * parameter as the reference's Parametrizable dumps it (Parametrizable.cpp:51-74):
+ * "- name (default: v) - doc[ - min: a][ - max: b]".  PMX_ICP_INVALID_ELEMENT for
+ * an unknown name, PMX_ICP_INVALID_PARAMETER when cap is too small. */
+int pmx_icp_outlier_filter_doc(int dtype, const char* name, char* out, int cap);
 int pmx_icp_set_default(pmx_icp* icp);
 int pmx_icp_load_yaml(pmx_icp* icp, const char* yaml_text);
 /* multi-GPU: call before the first compute; uid from pmx_comm_unique_id */

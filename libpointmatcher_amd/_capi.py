@@ -60,7 +60,7 @@ class Stats(C.Structure):
 # device-resident loop (pmx_loop_*)
 FILTER_KIND = {"default": 0, "NullOutlierFilter": 1, "MaxDistOutlierFilter": 2, "MinDistOutlierFilter": 3,
                "MedianDistOutlierFilter": 4, "TrimmedDistOutlierFilter": 5, "VarTrimmedDistOutlierFilter": 6,
-               "SurfaceNormalOutlierFilter": 8}
+               "SurfaceNormalOutlierFilter": 8, "GenericDescriptorOutlierFilter": 9}  # (9: filter_p[i] = soft, larger_than, threshold)
 CHECK_KIND = {"CounterTransformationChecker": 0, "DifferentialTransformationChecker": 1,
               "BoundTransformationChecker": 2}
 
@@ -167,6 +167,7 @@ EXPORTS = [
     "pmx_outlier_default", "pmx_outlier_null", "pmx_outlier_maxdist", "pmx_outlier_mindist",
     "pmx_outlier_mediandist", "pmx_outlier_trimmed", "pmx_outlier_vartrimmed", "pmx_outlier_robust",
     "pmx_robust_scale", "pmx_set_reading_radii", "pmx_set_reading_normals", "pmx_outlier_surface_normal",
+    "pmx_set_reference_weight_descriptor", "pmx_outlier_generic_descriptor",
     "pmx_p2plane_system", "pmx_p2plane_system_forced", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
@@ -211,6 +212,8 @@ def lib():
         l.pmx_set_reading_radii.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_set_reading_normals.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_outlier_surface_normal.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        l.pmx_set_reference_weight_descriptor.argtypes = [C.c_void_p, C.c_void_p]
+        l.pmx_outlier_generic_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
         l.pmx_p2plane_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         l.pmx_p2plane_system_forced.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         l.pmx_p2point_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -478,6 +481,17 @@ class Context:
             raise InvalidParameter(f"reading normals must be {self.N} x {self.rows - 1}, not {n.shape}")
         self._chk(self._l.pmx_set_reading_normals(self.h, _ptr(n) if n is not None else None))
 
+    def set_reference_weight_descriptor(self, desc):
+        """GenericDescriptorOutlierFilter: the reference's one-row descriptor, M values
+        in the order of set_reference's points, no NaN (None clears; so does the
+        next set_reference)."""
+        d = self._arr(desc).reshape(-1) if desc is not None else None
+        ref = getattr(self, "_ref_keep", None)
+        if d is not None and ref is not None and d.shape[0] != ref[0].shape[0]:
+            raise InvalidParameter(f"the weight descriptor must have {ref[0].shape[0]} values, "
+                                   f"not {d.shape[0]}")
+        self._chk(self._l.pmx_set_reference_weight_descriptor(self.h, _ptr(d) if d is not None else None))
+
     # --- per-iteration
     def set_search(self, search_type: int):
         """0 = brute force, 1/2 = exact grid search (KDTreeMatcher searchType)."""
@@ -518,6 +532,13 @@ class Context:
         if eps is None:
             eps = np.cos(self.dtype.type(max_angle))
         self._chk(self._l.pmx_outlier_surface_normal(self.h, pos, float(eps)))
+
+    def outlier_generic_descriptor(self, pos=0, soft=False, larger_than=True, threshold=0.1):
+        """GenericDescriptorOutlierFilter on the descriptor of
+        set_reference_weight_descriptor: hard (desc > threshold, or < with
+        larger_than False; strict, in the context's dtype) or soft (desc / max)."""
+        self._chk(self._l.pmx_outlier_generic_descriptor(self.h, pos, 1 if soft else 0, 1 if larger_than else 0,
+                                                         float(threshold)))
 
     def outlier_robust(self, pos=0, fct="cauchy", tuning=1.0, approximation=np.inf, scale_mode=RS_MAD,
                        berg_target=0.0, point2plane=False):

@@ -574,6 +574,32 @@ int pmx_cloud_label(const pmx_cloud* c, int which, int i, char* name, int cap, i
     return c->dtype == 1 ? get(c->d) : get(c->f);
 }
 
+// Parametrizable's documentation dump (Parametrizable.cpp:51-74) of a
+// registered outlier filter: "- name (default: v) - doc[ - min: a][ - max: b]" per line
+int pmx_icp_outlier_filter_doc(int dtype, const char* name, char* out, int cap) {
+    if (!name || !out || cap < 1 || (dtype != 0 && dtype != 1)) return PMX_ICP_INVALID_PARAMETER;
+    auto dump = [&](const auto& pm) -> int {
+        try {
+            const auto f = pm.OutlierFilterRegistrar.create(name);
+            std::string s;
+            for (const auto& p : f->parametersDoc) {
+                s += "- " + p.name + " (default: " + p.defaultValue + ") - " + p.doc;
+                if (!p.minValue.empty()) s += " - min: " + p.minValue;
+                if (!p.maxValue.empty()) s += " - max: " + p.maxValue;
+                s += "\n";
+            }
+            if ((int)s.size() >= cap) return PMX_ICP_INVALID_PARAMETER;
+            std::snprintf(out, (size_t)cap, "%s", s.c_str());
+            return PMX_ICP_OK;
+        } catch (const InvalidElement&) {
+            return PMX_ICP_INVALID_ELEMENT;
+        } catch (const std::exception&) {
+            return PMX_ICP_RUNTIME_ERROR;
+        }
+    };
+    return dtype == 1 ? dump(pm::PointMatcher<double>::get()) : dump(pm::PointMatcher<float>::get());
+}
+
 int pmx_cloud_data(const pmx_cloud* c, void* feat, void* desc) {
     if (!c) return PMX_ICP_INVALID_PARAMETER;
     if (c->dtype == 1)

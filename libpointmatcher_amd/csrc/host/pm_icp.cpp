@@ -446,6 +446,83 @@ struct SurfaceNormalOF : PM<T>::OutlierFilter {
     }
 };
 
+// GenericDescriptorOutlierFilter (OutlierFiltersImpl.h:196-221,
+// OutlierFiltersImpl.cpp:290-374): the weights on the device from a one-row
+// descriptor of the filtered reference, uploaded when the matcher is
+// initialised (initReference).  `source` chooses nothing: the reference reads
+// the filtered reference's descriptor in both branches (:322-325), and so does
+// this filter.
+template <typename T>
+struct GenericDescriptorOF : PM<T>::OutlierFilter {
+    const std::string source, descName;
+    const bool useSoftThreshold, useLargerThan;
+    const T threshold;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("source", "Point cloud from which the descriptor will be used: reference or reading", "reference"),
+                PDoc("descName", "Descriptor name used to weight paired points", "none"),
+                PDoc("useSoftThreshold",
+                     "If set to 1 (true), uses the value of the descriptor as a weight. If set to 0 (false), uses the "
+                     "parameter 'threshold' to set binary weights.",
+                     "0", "0", "1", &Parametrizable::Comp<bool>),
+                PDoc("useLargerThan",
+                     "If set to 1 (true), values over the 'threshold' will have a weight of one.  If set to 0 (false), "
+                     "values under the 'threshold' will have a weight of one. All other values will have a weight of "
+                     "zero.",
+                     "1", "0", "1", &Parametrizable::Comp<bool>),
+                PDoc("threshold", "Value used to determine the binary weights", "0.1", "0.0000001", "inf",
+                     &Parametrizable::Comp<T>)};
+    }
+    explicit GenericDescriptorOF(const Parametrizable::Parameters& p)
+        : PM<T>::OutlierFilter("GenericDescriptorOutlierFilter", doc(), p),
+          source(this->template get<std::string>("source")),
+          descName(this->template get<std::string>("descName")),
+          useSoftThreshold(this->template get<bool>("useSoftThreshold")),
+          useLargerThan(this->template get<bool>("useLargerThan")),
+          threshold(this->template get<T>("threshold")) {
+        if (source != "reference" && source != "reading")  // OutlierFiltersImpl.cpp:300-304
+            throw InvalidParameter("GenericDescriptorOutlierFilter: Error, the parameter named 'source' can only be "
+                                   "set to 'reference' or 'reading' but was set to " + source);
+    }
+    void checkReference(const DataPoints<T>& reference) const override {
+        if (!reference.descriptorExists(descName))  // getDescriptorViewByName, :327
+            throw InvalidField("Cannot find descriptor " + descName);
+        int span = 0;
+        for (auto& l : reference.descriptorLabels)
+            if (l.text == descName) span = l.span;
+        if (span != 1)  // :329-333
+            throw InvalidParameter("GenericDescriptorOutlierFilter: Error, the parameter named 'descName' must be a "
+                                   "1D descriptor but the field " + descName + " is " + std::to_string(span) + "D");
+    }
+    void initReference(Device& d, const DataPoints<T>& reference) override {
+        checkReference(reference);
+        const std::vector<T> v = reference.descriptor(descName);
+        d.check(pmx_set_reference_weight_descriptor(d.ctx, v.data()));
+    }
+    void compute(Device& d, const typename PM<T>::Matches&, int pos) override {
+        d.check(pmx_outlier_generic_descriptor(d.ctx, pos, useSoftThreshold ? 1 : 0, useLargerThan ? 1 : 0,
+                                               (double)threshold));
+    }
+    bool loopConfig(pmx_loop_cfg& cfg, int pos) const override {
+        cfg.filter_kind[pos] = PMX_FILTER_GENERICDESCRIPTOR;
+        cfg.filter_p[pos][0] = useSoftThreshold ? 1.0 : 0.0;
+        cfg.filter_p[pos][1] = useLargerThan ? 1.0 : 0.0;
+        cfg.filter_p[pos][2] = (double)threshold;
+        return true;
+    }
+};
+
+// The outlier chain against the filtered reference, on the host, before the
+// matcher indexes it.  One GenericDescriptorOutlierFilter per chain: the device
+// keeps one weight descriptor, and a second real-valued factor of this kind
+// would make the chain's product depend on the order (csrc/pmx_weight.h).
+template <typename T>
+void check_outlier_reference(const typename PM<T>::OutlierFilters& filters, const DataPoints<T>& reference) {
+    int generic = 0;
+    for (auto& f : filters) generic += f->className == "GenericDescriptorOutlierFilter" ? 1 : 0;
+    if (generic > 1) throw ConfigurationError("at most one GenericDescriptorOutlierFilter per outlier chain");
+    for (auto& f : filters) f->checkReference(reference);
+}
+
 // ---- error minimisers -----------------------------------------------------
 template <typename T>
 void build_p2plane_transform(int rows, const T* x, std::vector<T>& out) {
@@ -1425,6 +1502,8 @@ PointMatcher<T>::PointMatcher() {
                                true);
     OutlierFilterRegistrar.reg("SurfaceNormalOutlierFilter",
                                [](const Ps& p) { return std::make_shared<SurfaceNormalOF<T>>(p); }, true);
+    OutlierFilterRegistrar.reg("GenericDescriptorOutlierFilter",
+                               [](const Ps& p) { return std::make_shared<GenericDescriptorOF<T>>(p); }, true);
     ErrorMinimizerRegistrar.reg("PointToPlaneErrorMinimizer",
                                 [](const Ps& p) { return std::make_shared<PointToPlaneEM<T>>(p); }, true);
     ErrorMinimizerRegistrar.reg("PointToPlaneWithCovErrorMinimizer",
@@ -1651,6 +1730,7 @@ void PointMatcher<T>::ICP::prepare(const DataPoints& readingIn, const DataPoints
     T_refIn_refMean_.assign((size_t)dim * dim, (T)0);
     for (int i = 0; i < dim; ++i) T_refIn_refMean_[i * dim + i] = 1;
     T mean[3] = {0, 0, 0};
+    check_outlier_reference<T>(outlierFilters, reference);
     dev.ensure();
     mapIndexed_ = false;  // (an ICPSequence map is no longer the device's reference, even if init throws)
     matcher->init(dev, reference, nullptr, mean);  // ICP.cpp:302 (features - mean, ICP.cpp:299, on the device)
@@ -1794,6 +1874,7 @@ bool PointMatcher<T>::ICP::setMap(const DataPoints& inputCloud) {
     referenceDataPointsFilters.init();
     referenceDataPointsFilters.apply(map);
     if (map.n <= 0) throw ConvergenceError("empty reference");
+    check_outlier_reference<T>(outlierFilters, map);
     dev.ensure();
     matcher->init(dev, map);  // ICP.cpp:503 (the grid stays on the device)
     keepReferenceDescriptors(map);
@@ -1902,6 +1983,8 @@ void PointMatcher<T>::ICP::keepReadingNoise(const DataPoints& reading) {
 
 template <typename T>
 void PointMatcher<T>::ICP::keepReferenceDescriptors(const DataPoints& reference) {
+    // (the matcher has just indexed this cloud: the filters' device inputs from it)
+    for (auto& f : outlierFilters) f->initReference(dev, reference);
     refNoise_.reset();
     refDens_.reset();
     for (const char* name : {"simpleSensorNoise", "densities"}) {

@@ -101,6 +101,11 @@ struct PointMatcher {
         // the filter reads the reading's "normals" descriptor on the device
         // (SurfaceNormalOutlierFilter): the ICP uploads it with the reading
         virtual bool needsReadingNormals() const { return false; }
+        // what the filter reads of the filtered reference
+        // (GenericDescriptorOutlierFilter's descriptor): checked on the host
+        // before the matcher indexes the cloud, uploaded once it has
+        virtual void checkReference(const DataPoints& /*filteredReference*/) const {}
+        virtual void initReference(Device& /*dev*/, const DataPoints& /*filteredReference*/) {}
     };
     struct OutlierFilters : std::vector<std::shared_ptr<OutlierFilter>> {
         void compute(Device& dev, const Matches& m);  // OutlierFilter.cpp:63-103

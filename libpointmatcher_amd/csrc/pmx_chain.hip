@@ -260,6 +260,7 @@ int build_grid(pmx_ctx* c, int64_t M, const std::function<int()>& before_levels 
         GridLevel L = keep[l];
         keep[l] = GridLevel{};
         L.ppc = c->level_ppc[l];
+        L.gw_valid = false;  // (a kept buffer holds the last reference's permutation)
         c->levels.push_back(L);
     }
     gt.mark("sizing");
@@ -276,6 +277,27 @@ int cold_level(const pmx_ctx* c) {
             std::fabs(std::log(c->level_ppc[(size_t)best] / c->first_ppc)))
             best = l;
     return best;
+}
+
+// GenericDescriptorOutlierFilter: level l's copy of the reference's weight
+// descriptor in position order (match ids then index it directly), on the
+// stream that builds the level
+template <typename T>
+int permute_wdesc(pmx_ctx* c, int l, hipStream_t st) {
+    GridLevel& L = c->levels[(size_t)l];
+    const size_t bytes = sizeof(T) * (size_t)std::max<int64_t>(c->grid_valid, 1);
+    if (!L.gw || L.cap_gw < bytes) {
+        if (L.gw) (void)hipFree(L.gw);
+        L.gw = nullptr;
+        L.cap_gw = 0;
+        HIPCHK(c, hipMalloc(&L.gw, bytes));
+        L.cap_gw = bytes;
+    }
+    L.gw_valid = false;
+    launch_gd_permute<T>((const T*)c->d_wdesc, L.gidx, c->grid_valid, (T*)L.gw, st);
+    HIPCHK(c, hipGetLastError());
+    L.gw_valid = true;
+    return PMX_OK;
 }
 
 // one level of the current reference: buffers, the build enqueued on `st`
@@ -319,14 +341,17 @@ int build_one_level(pmx_ctx* c, int l, const SetupScratch& sc, hipStream_t st) {
         L.dim[a] = s.g[a];
     }
     L.h = s.h;
+    // (a level built after the weight descriptor's upload: its copy behind the build)
+    if (c->has_wdesc) return permute_wdesc<T>(c, l, st);
     return PMX_OK;
 }
 
-// a grid level as the kernels see it
+// a grid level as the kernels see it (gw: the context holds a weight descriptor)
 template <typename T>
-GridDesc<T> level_desc(const GridLevel& L) {
+GridDesc<T> level_desc(const GridLevel& L, bool gw) {
     return {(const P4<T>*)L.gpts, (const P4<T>*)L.gpn, L.gidx, L.gstart,
-            {{L.lo[0], L.lo[1], L.lo[2]}, L.h, 1.0 / L.h, {L.dim[0], L.dim[1], L.dim[2]}}};
+            {{L.lo[0], L.lo[1], L.lo[2]}, L.h, 1.0 / L.h, {L.dim[0], L.dim[1], L.dim[2]}},
+            gw && L.gw_valid ? (const T*)L.gw : nullptr};
 }
 
 // the device table of levels [0, levels_built) (the device loop picks the
@@ -341,7 +366,7 @@ int publish_levels(pmx_ctx* c) {
     }
     HIPCHK(c, hipEventSynchronize(c->table_ev));  // (the previous table's copy has read the staging)
     GridDesc<T>* tab = (GridDesc<T>*)c->h_table;
-    for (size_t l = 0; l < (size_t)c->levels_built; ++l) tab[l] = level_desc<T>(c->levels[l]);
+    for (size_t l = 0; l < (size_t)c->levels_built; ++l) tab[l] = level_desc<T>(c->levels[l], c->has_wdesc);
     if (!c->d_gdesc) HIPCHK(c, hipMalloc(&c->d_gdesc, sizeof(GridDesc<T>) * kMaxLevels));
     // (stream-ordered and asynchronous: the host goes on — the reading's
     // upload overlaps the level builds still running)
@@ -511,6 +536,7 @@ int set_reference_impl(pmx_ctx* c, const T* feat, int rows, int64_t M, const T* 
     // builds, which interleave them (before_levels).
     c->has_normals = normals != nullptr;
     c->has_ref_noise = c->has_ref_dens = false;  // (a new reference: its descriptors, if any, follow)
+    c->has_wdesc = false;
     std::thread nrm_thread;
     int nrm_rc = PMX_OK;
     const size_t nrm_bytes = sizeof(T) * (size_t)D * M;
@@ -837,7 +863,7 @@ int match_grid(pmx_ctx* c, const Mat4<T>& Tm, int knn, T maxR2, hipEvent_t e0, h
                        c->d_vpart != nullptr};
     const GridMatchPlan plan = plan_grid_match(f);
 
-    GridDesc<T> D = level_desc<T>(L);
+    GridDesc<T> D = level_desc<T>(L, c->has_wdesc);
     if (!plan.nbr_normals) D.gpn = nullptr;
     MatchQuery<T> Q{(const P4<T>*)c->d_rd, c->N, Tm, knn, maxR2, c->has_radii ? (const T*)c->d_radii : nullptr,
                     c->d_waves, c->n_waves, c->tile_max};
@@ -1006,6 +1032,7 @@ MatchView<T> match_view(const pmx_ctx* c) {
         m.nrm = m.pn ? m.pn + 1 : nullptr;  // (null: a reference without normals)
         m.rs = 2;
         m.gidx = lv.gidx;
+        m.gw = c->has_wdesc && lv.gw_valid ? (const T*)lv.gw : nullptr;
         // k = 1 after a match that left its neighbour records with the normals
         // (d_nbr: points, then normals, in slot order)
         if (c->nbr_prev && c->nbr_normals && c->knn == 1) m.nbr = (const P4<T>*)c->d_nbr;
@@ -1013,6 +1040,7 @@ MatchView<T> match_view(const pmx_ctx* c) {
         m.ref = m.pn = (const P4<T>*)c->d_ref;
         m.nrm = (const P4<T>*)c->d_nrm;
         m.rs = 1;
+        m.gw = c->has_wdesc ? (const T*)c->d_wdesc : nullptr;
     }
     return m;
 }
@@ -1091,6 +1119,7 @@ int unpermute(pmx_ctx* c, const std::vector<V>& src, V* dst, int k) {
 // record predicate `pos` of the weight chain (position 0 starts a new chain)
 void chain_set(pmx_ctx* c, int pos, int type, double thr) {
     if (pos == 0 || c->rb_pos >= pos) c->rb_pos = -1;  // (a new chain, or the robust filter's position rewritten)
+    if (pos == 0 || c->gd_pos >= pos) c->gd_pos = -1;  // (likewise the GenericDescriptor filter's)
     c->chain_n = pos + 1;
     c->chain_type[pos] = type;
     c->chain_thr[pos] = thr;
@@ -1133,6 +1162,13 @@ WChain<T> chain_of(const pmx_ctx* c) {
             w.sn.rs = m.rs;
             w.sn.dim = c->dim;
         }
+    }
+    // GenericDescriptorOutlierFilter: the descriptor in the order of the match's ids
+    if (c->gd_pos >= 0 && c->gd_pos < c->chain_n) {
+        w.gd.desc = match_view<T>(c).gw;
+        w.gd.mode = c->gd_mode;
+        w.gd.thr = (T)c->gd_thr;
+        w.gd.m = c->gd_max();
     }
     return w;
 }
@@ -1320,6 +1356,76 @@ int outlier_robust_impl(pmx_ctx* c, int pos, int fct, double tuning, double appr
     return PMX_OK;
 }
 
+// GenericDescriptorOutlierFilter::compute (OutlierFiltersImpl.cpp:312-374) for
+// the resident match: the filter joins the chain as its descriptor factor
+// (gd_weight, pmx_weight.h); the soft form's maximum over all entries is
+// reduced now, on the device, and over the ranks
+template <typename T>
+int outlier_generic_impl(pmx_ctx* c, int pos, int soft, int larger_than, double threshold) {
+    int rc = check_match(c);
+    if (rc) return rc;
+    if (pos < 0 || pos >= kMaxChain) return fail(c, PMX_E_BAD_PARAM, "outlier chain longer than 8 filters");
+    if (pos > c->chain_n) return fail(c, PMX_E_BAD_PARAM, "outlier chain positions must be consecutive");
+    if (c->gd_pos >= 0 && c->gd_pos < pos && pos <= c->chain_n)
+        return fail(c, PMX_E_BAD_PARAM, "one GenericDescriptorOutlierFilter per outlier chain");
+    if (!c->has_wdesc)
+        return fail(c, PMX_E_STATE, "GenericDescriptorOutlierFilter: pmx_set_reference_weight_descriptor must be called first");
+    // (the copy the ids of this match index; the device loop: of every level it may choose)
+    if (!match_view<T>(c).gw)
+        return fail(c, PMX_E_STATE, "GenericDescriptorOutlierFilter: the match's grid level holds no copy of the weight descriptor");
+    if (c->loop_on)
+        for (int l = 0; l < c->levels_built; ++l)
+            if (!c->lv(l).gw_valid)
+                return fail(c, PMX_E_STATE, "GenericDescriptorOutlierFilter: a grid level holds no copy of the weight descriptor");
+    if (!c->d_gdm) {
+        HIPCHK(c, hipMalloc(&c->d_gdm, 256));
+        HIPCHK(c, hipMemsetAsync(c->d_gdm, 0, 256, c->stream));
+    }
+    chain_set(c, pos, kWPGeneric, 0.0);
+    c->gd_pos = pos;
+    c->gd_mode = soft ? kGDSoft : (larger_than ? kGDGreater : kGDLess);
+    c->gd_thr = (double)(T)threshold;
+    if (soft) {
+        launch_gd_max<T>(c->d_ids, c->N * c->knn, match_view<T>(c).gw, c->d_partials, c->gd_ticket(), c->gd_max(),
+                         loop_ctl(c), (const GridDesc<T>*)c->d_gdesc, c->stream);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = coll_allreduce(c, c->gd_max(), 1, PMX_COLL_F64, PMX_COLL_MAX))) return rc;
+    }
+    return PMX_OK;
+}
+
+// the reference's weight descriptor, M values in original id order, and every
+// built grid level's copy of it in position order
+template <typename T>
+int set_reference_wdesc_impl(pmx_ctx* c, const T* desc) {
+    c->w_valid = false;
+    if (!desc) {
+        if (c->has_wdesc && c->grid_ready) {
+            c->has_wdesc = false;
+            return publish_levels<T>(c);  // (the level table without the copies)
+        }
+        c->has_wdesc = false;
+        return PMX_OK;
+    }
+    if (!c->d_ref) return fail(c, PMX_E_STATE, "pmx_set_reference must be called first");
+    const size_t bytes = sizeof(T) * (size_t)c->M;
+    int rc;
+    (void)hipStreamSynchronize(c->stream);  // (kernels of an earlier chain may still read the old values)
+    if ((rc = ensure(c, &c->d_wdesc, &c->wdesc_bytes, bytes))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_wdesc, desc, bytes, hipMemcpyHostToDevice, c->stream));
+    c->has_wdesc = true;
+    for (auto& L : c->levels) L.gw_valid = false;
+    // (whatever the search type now is: pmx_set_search may change it before the next match)
+    if (c->grid_ready) {
+        side_join(c);  // (the side stream's levels: their gidx)
+        for (int l = 0; l < c->levels_built; ++l)
+            if ((rc = permute_wdesc<T>(c, l, c->stream))) return rc;
+        if ((rc = publish_levels<T>(c))) return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's buffer may go)
+    return PMX_OK;
+}
+
 template <typename T>
 int set_radii_impl(pmx_ctx* c, const T* radii) {
     if (!radii) {
@@ -1432,10 +1538,10 @@ int select_reset(pmx_ctx* c) {
 // one D2H copy of the iteration block, then a stream sync
 int readback(pmx_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(c->h_result, c->d_result, kBlkCopy, hipMemcpyDeviceToHost, c->stream));
-    // A chain with the SurfaceNormalOutlierFilter reports the threshold of its
-    // last quantile filter wherever that stands: the normal filter reads no
-    // distance, so [SurfaceNormal, Trimmed] and [Trimmed, SurfaceNormal] must
-    // report the same limit.  Only such chains: every other chain keeps
+    // A chain with a filter that reads no distance (SurfaceNormalOutlierFilter,
+    // GenericDescriptorOutlierFilter) reports the threshold of its last
+    // quantile filter wherever that stands: [SurfaceNormal, Trimmed] and
+    // [Trimmed, SurfaceNormal] must report the same limit.  Only such chains: every other chain keeps
     // reporting position 0's select state, as it always has (callers may read
     // that diagnostic), and issues no copy beyond the iteration block.  The
     // select state of a later position lies outside the iteration block, so
@@ -1443,12 +1549,12 @@ int readback(pmx_ctx* c) {
     // the 8 bytes at kBlkCopy, past everything the block copy writes
     // (h_result is kBlkBytes long; module_limit reads them back).
     c->limit_pos = 0;
-    bool sn = false;
+    bool no_dist = false;  // (the chain holds a filter that reads no distance)
     for (int i = 0; i < c->chain_n; ++i) {
-        sn = sn || c->chain_type[i] == kWPNormal;
+        no_dist = no_dist || c->chain_type[i] == kWPNormal || c->chain_type[i] == kWPGeneric;
         if (c->chain_type[i] == kWPState) c->limit_pos = i;
     }
-    if (!sn) c->limit_pos = 0;
+    if (!no_dist) c->limit_pos = 0;
     if (c->limit_pos > 0)
         HIPCHK(c, hipMemcpyAsync((char*)c->h_result + kBlkCopy, &c->sel_slot(c->limit_pos)->limit, sizeof(double),
                                  hipMemcpyDeviceToHost, c->stream));
@@ -1527,7 +1633,7 @@ int p2plane_enqueue(pmx_ctx* c, int force, PendingSums* last) {
                               (const GridDesc<T>*)c->d_gdesc, c->vpart_dirty ? c->d_vpart : nullptr, c->stream);
     c->vpart_dirty = false;
     HIPCHK(c, hipGetLastError());
-    *last = {c->d_result, p2plane_nv(form, chain.robust)};
+    *last = {c->d_result, p2plane_nv(form, chain.real())};
     return PMX_OK;
 }
 
@@ -1589,7 +1695,7 @@ int p2plane_impl(pmx_ctx* c, int force, double* A, double* b, pmx_stats* st) {
     if (rc) return rc;
     if (!c->has_normals)
         return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer requires \"normals\" on the reference");
-    const bool full = c->rb_pos >= 0 && c->rb_pos < c->chain_n;  // (the weighted layout, see p2plane_enqueue)
+    const bool full = c->chain_real();  // (the weighted layout, see p2plane_enqueue)
     PendingSums last;
     if ((rc = p2plane_enqueue<T>(c, force, &last))) return rc;
     if ((rc = finish_sums(c, last))) return rc;
@@ -1803,6 +1909,7 @@ int get_weights_impl(pmx_ctx* c, void* w) {
     template int match_impl<T>(pmx_ctx*, const T*, int, double, uint64_t*);                  \
     template int outlier_impl<T>(pmx_ctx*, int, int, double, double, double);               \
     template int outlier_robust_impl<T>(pmx_ctx*, int, int, double, double, int, double, int); \
+    template int outlier_generic_impl<T>(pmx_ctx*, int, int, int, double);                  \
     template int p2plane_enqueue<T>(pmx_ctx*, int, PendingSums*);                           \
     template int p2point_enqueue<T>(pmx_ctx*, bool, PendingSums*);                          \
     template int p2plane_cov_impl<T>(pmx_ctx*, const T*, double*, double*, int64_t*);       \
@@ -1884,6 +1991,13 @@ int pmx_set_reference_descriptors(pmx_ctx* c, const void* noise, const void* den
                     set_reference_descriptors_impl<double>(c, (const double*)noise, (const double*)densities));
 }
 
+int pmx_set_reference_weight_descriptor(pmx_ctx* c, const void* desc) {
+    if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c, set_reference_wdesc_impl<float>(c, (const float*)desc),
+                    set_reference_wdesc_impl<double>(c, (const double*)desc));
+}
+
 int pmx_match(pmx_ctx* c, const void* T_iter, int knn, double maxDist, double epsilon, uint64_t* visited) {
     if (!c || !T_iter) return fail(c, PMX_E_BAD_PARAM, "null argument");
     if (!(epsilon >= 0)) return fail(c, PMX_E_BAD_PARAM, "epsilon must be >= 0");
@@ -1945,6 +2059,11 @@ int pmx_outlier_robust(pmx_ctx* c, int pos, int fct, double tuning, double appro
     if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
     return DISPATCH(c, outlier_robust_impl<float>(c, pos, fct, tuning, approx, mode, target, p2pl),
                     outlier_robust_impl<double>(c, pos, fct, tuning, approx, mode, target, p2pl));
+}
+int pmx_outlier_generic_descriptor(pmx_ctx* c, int pos, int soft, int larger_than, double threshold) {
+    if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    return DISPATCH(c, outlier_generic_impl<float>(c, pos, soft, larger_than, threshold),
+                    outlier_generic_impl<double>(c, pos, soft, larger_than, threshold));
 }
 int pmx_robust_scale(pmx_ctx* c, int pos, double* scale) {
     if (!c || !scale) return fail(c, PMX_E_BAD_PARAM, "null argument");

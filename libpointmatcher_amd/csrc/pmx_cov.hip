@@ -5,8 +5,8 @@
 //
 // One launch per ICP, after the loop stopped: it walks the match arrays the
 // last point-to-plane reduction walked, with the same kept rule (dist != inf
-// and a non-zero chain weight, the SurfaceNormal predicate included; a robust
-// chain's weight only decides kept / not kept, the reference's estimate reads
+// and a non-zero chain weight, the SurfaceNormal and GenericDescriptor
+// factors included; a real-valued weight only decides kept / not kept, the reference's estimate reads
 // no weight), the same id source and, at k = 1, the match's neighbour records.
 // Bytes per pair as p2plane_partial: reading 16, dist 4, point and normal
 // record 32 in slot order (or id 4 and two 16-byte gathers) in float.  The T
@@ -21,15 +21,16 @@ namespace pmx {
 // entry (slot i, distance dv, id) is a column of ErrorElements: dist != inf
 // and w != 0 (ErrorMinimizer.cpp:75-131) for the chain's weight w (entry_weight,
 // pmx_weight.h; q, n: the matched records as loaded, rn: the reading's normal)
-template <typename T, bool SN>
+template <typename T, bool SN, bool GD>
 __device__ __forceinline__ bool cov_kept(const WChain<T>& chain, const WRange<T>& wr, const Mat4<T>& Tm, T dv,
                                          int32_t id, const P4<T>& rn, T px, T py, T pz, const P4<T>& q,
                                          const P4<T>& n) {
     if (dv == (T)__builtin_huge_val()) return false;
-    return entry_weight<T, SN>(chain, chain.sn, wr, Tm, dv, id, px, py, pz, q, loaded(n), loaded(rn)) != (T)0;
+    return entry_weight<T, SN, true, GD>(chain, chain.sn, wr, Tm, dv, id, px, py, pz, q, loaded(n), loaded(rn),
+                                         chain.gd) != (T)0;
 }
 
-template <typename T, bool SN>
+template <typename T, bool SN, bool GD>
 __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                           const P4<T>* __restrict__ ref,
                                                           const P4<T>* __restrict__ nrm, int rs,
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     // whether an entry's records are worth gathering: without the robust
     // filter a rejecting predicate makes the weight 0 (with it, 0 * NaN is not)
-    const auto may_keep = [&](T dv) { return dv != inf && (chain.robust || chain_keep(wr, dv)); };
+    const auto may_keep = [&](T dv) { return dv != inf && ((GD ? chain.real() : chain.robust != 0) || chain_keep(wr, dv)); };
     int64_t i0 = (int64_t)xcd_block() * blockDim.x + threadIdx.x;
     if (k == 1) {
         // k = 1: U slots per round, every load that needs no id issued up
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
                 if (nbr) {
                     q[u] = nbr[jj];
                     n[u] = nbr[N + jj];
-                    if (SN) id[u] = ids[jj];
+                    if (SN || GD) id[u] = ids[jj];
                 } else {
                     id[u] = ids[jj];
                 }
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
                 if (i0 + u * stride >= N) continue;
                 T px, py, pz;
                 xform3(Tm, r[u], px, py, pz);
-                if (!cov_kept<T, SN>(chain, wr, Tm, dv[u], id[u], rn[SN ? u : 0], px, py, pz, q[u], n[u])) continue;
+                if (!cov_kept<T, SN, GD>(chain, wr, Tm, dv[u], id[u], rn[SN ? u : 0], px, py, pz, q[u], n[u])) continue;
                 acc[kCovCount] += 1.0;
                 cov_add<T, true, true, kCovQ, NV>(acc, px, py, pz, q[u], n[u], cp);
             }
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
             const int32_t id = ids[e];
             const int64_t g = (int64_t)(id >= 0 ? id : 0) * rs;
             const P4<T> q = gld(ref, g), n = gld(nrm, g);
-            if (!cov_kept<T, SN>(chain, wr, Tm, dv, id, rn, px, py, pz, q, n)) continue;
+            if (!cov_kept<T, SN, GD>(chain, wr, Tm, dv, id, rn, px, py, pz, q, n)) continue;
             acc[kCovCount] += 1.0;
             cov_add<T, true, true, kCovQ, NV>(acc, px, py, pz, q, n, cp);
         }
@@ -117,9 +118,11 @@ __global__ __launch_bounds__(256) void p2plane_cov_kernel(const P4<T>* __restric
 template <typename T>
 void launch_p2plane_cov(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, const CovParams<T>& cp,
                         double* partials, hipStream_t s) {
-    auto* const kern = chain.sn.rn ? p2plane_cov_kernel<T, true> : p2plane_cov_kernel<T, false>;
-    // (the neighbour records where the last point-to-plane reduction read them: k = 1, no robust filter)
-    const P4<T>* nbr = m.k == 1 && !chain.robust ? m.nbr : nullptr;
+    const bool gd = chain.gd.desc != nullptr;
+    auto* const kern = gd ? (chain.sn.rn ? p2plane_cov_kernel<T, true, true> : p2plane_cov_kernel<T, false, true>)
+                          : (chain.sn.rn ? p2plane_cov_kernel<T, true, false> : p2plane_cov_kernel<T, false, false>);
+    // (the neighbour records where the last point-to-plane reduction read them: k = 1, no real-valued weights)
+    const P4<T>* nbr = m.k == 1 && !chain.real() ? m.nbr : nullptr;
     hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k, m.N,
                        cp.alpha, cp.beta, cp.gamma, cp.tx, cp.ty, cp.tz, partials, nbr);
 }

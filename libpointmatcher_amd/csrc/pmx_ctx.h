@@ -65,13 +65,19 @@ struct GridLevel {
     // allocated capacities (a new reference reuses the buffers when it fits:
     // hipMalloc / hipFree of 4 buffers x 6 levels was a large part of setup)
     size_t cap_pts = 0, cap_gpn = 0, cap_idx = 0, cap_start = 0;
+    // the reference's weight descriptor in position order (GenericDescriptorOutlierFilter;
+    // valid while pmx_ctx::has_wdesc)
+    void* gw = nullptr;
+    size_t cap_gw = 0;
+    bool gw_valid = false;  // gw is the current descriptor in this level's current order
     void release() {
-        for (void* b : {gpts, gpn, (void*)gidx, (void*)gstart})
+        for (void* b : {gpts, gpn, (void*)gidx, (void*)gstart, gw})
             if (b) (void)hipFree(b);
-        gpts = gpn = nullptr;
+        gpts = gpn = gw = nullptr;
         gidx = nullptr;
         gstart = nullptr;
-        cap_pts = cap_gpn = cap_idx = cap_start = 0;
+        cap_pts = cap_gpn = cap_idx = cap_start = cap_gw = 0;
+        gw_valid = false;
     }
 };
 
@@ -212,6 +218,12 @@ struct pmx_ctx {
     void* d_ref_dens = nullptr;
     size_t ref_noise_bytes = 0, ref_dens_bytes = 0;
     bool has_ref_noise = false, has_ref_dens = false;
+    // GenericDescriptorOutlierFilter: the reference's one-row weight descriptor
+    // in original id order (pmx_set_reference_weight_descriptor: T[M]); every
+    // built grid level holds its copy in position order (GridLevel::gw)
+    void* d_wdesc = nullptr;
+    size_t wdesc_bytes = 0;
+    bool has_wdesc = false;
 
     // matches / weights
     int knn = 0;
@@ -243,6 +255,17 @@ struct pmx_ctx {
     double* rob_scale(int pos) const { return (double*)((char*)d_rob + 256) + pos; }
     double* rob_sums() const { return (double*)((char*)d_rob + 256) + kMaxChain; }
     SelectState* rob_sel() const { return (SelectState*)d_rob; }
+    // GenericDescriptorOutlierFilter (at most one per chain): its mode (GDMode)
+    // and threshold, and the device block of its soft form: the maximum m (a
+    // T value as double), then the max reduction's ticket at byte 64
+    int gd_pos = -1, gd_mode = 0;
+    double gd_thr = 0.0;
+    void* d_gdm = nullptr;
+    double* gd_max() const { return (double*)d_gdm; }
+    unsigned int* gd_ticket() const { return (unsigned int*)((char*)d_gdm + 64); }
+    bool gd_soft() const { return gd_pos >= 0 && gd_pos < chain_n && gd_mode == kGDSoft; }
+    // the chain holds real-valued weights (the weighted sums' layout)
+    bool chain_real() const { return (rb_pos >= 0 && rb_pos < chain_n) || gd_soft(); }
 
     // quantile select: SelectState followed by the per-iteration error word;
     // chain positions >= 1 use their own states (d_sel_more)
@@ -423,6 +446,8 @@ int outlier_impl(pmx_ctx* c, int kind, int chain_pos, double p0, double p1, doub
 template <typename T>
 int outlier_robust_impl(pmx_ctx* c, int pos, int fct, double tuning, double approx, int mode, double target,
                         int p2pl);
+template <typename T>
+int outlier_generic_impl(pmx_ctx* c, int pos, int soft, int larger_than, double threshold);
 // The minimisers' reductions enqueued, all but the last one's sum: *last names the partials
 // still to be finalized into out[0, nv), by finish_sums or the loop's fused finalize + step.
 struct PendingSums {

@@ -151,6 +151,7 @@ struct GridDesc {
     const int32_t* gidx;
     const uint32_t* start;
     GridGeom G;
+    const T* gw;  // the reference's weight descriptor in position order (GenericDescriptorOutlierFilter; null: none)
 };
 // Per-context control word of the device-resident ICP loop (pmx_loop.hip):
 // every kernel of an enqueued iteration reads it first.  done != 0 makes the
@@ -423,6 +424,7 @@ struct MatchView {
     // launcher decides whether its kernel reads them in place of the gather.
     const P4<T>* nbr;
     const int32_t* gidx;  // ids -> original reference ids (null: they are)
+    const T* gw;          // the reference's weight descriptor in the order of the ids (null: none uploaded)
 };
 
 // ---- reductions (pmx_reduce.hip) ----
@@ -457,5 +459,18 @@ void launch_p2point_pass2(const MatchView<T>& m, const Mat4<T>& Tm, const WChain
 // SurfaceNormal factor included): the host mirror and what reads it
 template <typename T>
 void launch_weights_chain(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, T* w, hipStream_t s);
+
+// ---- GenericDescriptorOutlierFilter (pmx_generic.hip) ----
+// a grid level's copy of the reference's weight descriptor: out[pos] = desc[gidx[pos]]
+template <typename T>
+void launch_gd_permute(const T* desc, const int32_t* gidx, int64_t n, T* out, hipStream_t s);
+// soft mode's m = max over the match's entries of (id valid ? desc[id] : 0),
+// a T value stored as double at *out.  partials: kGDMaxBlocks doubles;
+// ticket: one zeroed word (left zero).  ctl / gd (device loop): early exit, and
+// the descriptor copy of the level whose positions the ids are.
+constexpr int kGDMaxBlocks = 256;
+template <typename T>
+void launch_gd_max(const int32_t* ids, int64_t n, const T* desc, double* partials, unsigned int* ticket, double* out,
+                   const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s);
 
 }  // namespace pmx

@@ -48,13 +48,18 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     if (!(cfg->max_dist >= 0)) return fail(c, PMX_E_BAD_PARAM, "maxDist must be >= 0");
     if (cfg->n_filters < 0 || cfg->n_filters > kMaxChain)
         return fail(c, PMX_E_BAD_PARAM, "device loop: at most 8 outlier filters");
-    int n_robust = 0, n_normal = 0;
+    int n_robust = 0, n_normal = 0, n_generic = 0;
+    bool soft = false;  // (a soft GenericDescriptorOutlierFilter: real-valued weights)
     for (int i = 0; i < cfg->n_filters; ++i) {
         const int k = cfg->filter_kind[i];
         const double* p = cfg->filter_p[i];
-        if (k < PMX_FILTER_DEFAULT || k > PMX_FILTER_SURFACENORMAL || (k == PMX_FILTER_DEFAULT && i != 0))
+        if (k < PMX_FILTER_DEFAULT || k > PMX_FILTER_GENERICDESCRIPTOR || (k == PMX_FILTER_DEFAULT && i != 0))
             return fail(c, PMX_E_BAD_PARAM, "device loop: unknown outlier filter");
         if (k == PMX_FILTER_SURFACENORMAL) ++n_normal;
+        if (k == PMX_FILTER_GENERICDESCRIPTOR) {
+            ++n_generic;
+            soft = soft || p[0] != 0.0;
+        }
         if (k == PMX_FILTER_ROBUST) {
             ++n_robust;
             if (cfg->robust_fct < PMX_RF_CAUCHY || cfg->robust_fct > PMX_RF_STUDENT ||
@@ -74,6 +79,13 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     }
     if (n_robust > 1) return fail(c, PMX_E_BAD_PARAM, "device loop: one RobustOutlierFilter per chain");
     if (n_normal > 1) return fail(c, PMX_E_BAD_PARAM, "device loop: one SurfaceNormalOutlierFilter per chain");
+    if (n_generic > 1) return fail(c, PMX_E_BAD_PARAM, "device loop: one GenericDescriptorOutlierFilter per chain");
+    if (n_generic && !c->has_wdesc)
+        return fail(c, PMX_E_STATE, "GenericDescriptorOutlierFilter: pmx_set_reference_weight_descriptor must be called first");
+    if (n_generic)  // (the loop picks its level on the device, among the built ones: each needs its copy)
+        for (int l = 0; l < c->levels_built; ++l)
+            if (!c->lv(l).gw_valid)
+                return fail(c, PMX_E_STATE, "GenericDescriptorOutlierFilter: a grid level holds no copy of the weight descriptor");
     if (cfg->minimizer != 0 && cfg->minimizer != 1) return fail(c, PMX_E_BAD_PARAM, "device loop: unknown minimizer");
     if (cfg->minimizer == 0 && !c->has_normals)
         return fail(c, PMX_E_BAD_PARAM, "PointToPlaneErrorMinimizer requires \"normals\" on the reference");
@@ -102,7 +114,7 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     // (force2D on a 2-D cloud changes nothing: the unforced step)
     if (c->dim == 3 && cfg->force == PMX_FORCE_2D) d.minimizer = kStepForce2D;
     if (c->dim == 3 && cfg->force == PMX_FORCE_4DOF) d.minimizer = kStepForce4DOF;
-    d.full = n_robust > 0 ? 1 : 0;  // (point-to-plane: the weighted system's full A layout)
+    d.full = n_robust > 0 || soft ? 1 : 0;  // (point-to-plane: the weighted system's full A layout)
     d.n_checkers = cfg->n_checkers;
     for (int i = 0; i < cfg->n_checkers; ++i) {
         d.checker_kind[i] = cfg->checker_kind[i];
@@ -242,7 +254,12 @@ int loop_enqueue_iteration(pmx_ctx* c) {
     // Sharded: the counter phase packs the window segment the all-gather
     // sends, so it stays a launch of its own before the collective.
     const int k0 = cfg.n_filters > 0 ? cfg.filter_kind[0] : -1;
-    c->merge_counter = c->spec_on && !sharded(c) && cfg.minimizer == 0 && c->grid_mode >= 1 && c->N > 0 &&
+    // (not with a soft GenericDescriptorOutlierFilter: the weighted point-to-plane
+    // kernel does not zero the spread counters)
+    bool gd_soft = false;
+    for (int i = 0; i < cfg.n_filters; ++i)
+        gd_soft = gd_soft || (cfg.filter_kind[i] == PMX_FILTER_GENERICDESCRIPTOR && cfg.filter_p[i][0] != 0.0);
+    c->merge_counter = c->spec_on && !sharded(c) && cfg.minimizer == 0 && c->grid_mode >= 1 && c->N > 0 && !gd_soft &&
                        cfg.knn <= kLaneMaxK && (k0 == PMX_FILTER_TRIMMED || k0 == PMX_FILTER_MEDIANDIST);
     // no quantile window (a MaxDist chain, or none): the counter phase runs
     // in the fused finalize + step launch instead (one launch fewer; the
@@ -288,6 +305,10 @@ int loop_enqueue_iteration(pmx_ctx* c) {
             if ((rc = outlier_robust_impl<T>(c, i, cfg.robust_fct, cfg.robust_tuning, cfg.robust_approx, mode,
                                              cfg.robust_berg_target, cfg.robust_p2pl)))
                 return rc;
+            continue;
+        }
+        if (cfg.filter_kind[i] == PMX_FILTER_GENERICDESCRIPTOR) {  // (soft: the maximum of this iteration's match)
+            if ((rc = outlier_generic_impl<T>(c, i, p[0] != 0.0, p[1] != 0.0, p[2]))) return rc;
             continue;
         }
         if ((rc = outlier_impl<T>(c, cfg.filter_kind[i], i, p[0], p[1], p[2]))) return rc;

@@ -137,16 +137,20 @@ constexpr int kGatherK = 4;
 // every entry's id and the reading's normal are loaded as well, the gathered
 // reference normal serves both the predicate and F, and a pair counts as kept
 // only when both predicates pass (the product of the weights)
-// The keep test below is entry_weight<T, SN>(...) != 0 (pmx_weight.h, the
-// definition) for a chain without the robust filter, which is all this body
-// is launched for: chain_keep(dv) && (!SN || (id >= 0 && sn_pass)).  It stays
-// written out, once per k range, around each range's own order of loads.
-template <typename T, int DIM, bool SN = false>
+// GD: the chain holds a hard GenericDescriptorOutlierFilter (gdp: chain.gd, or
+// its copy bound to the device loop's level): every entry's id is loaded as
+// well, and the pair's descriptor value is gathered by it.
+// The keep test below is entry_weight<T, SN, true, GD>(...) != 0 (pmx_weight.h,
+// the definition) for a chain of 0/1 factors, which is all this body is
+// launched for: pair_keep (pmx_weight.h), called once per k range around each
+// range's own order of loads.
+template <typename T, int DIM, bool SN = false, bool GD = false>
 __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const Mat4<T>& Tm,
                                              const P4<T>* __restrict__ ref, const P4<T>* __restrict__ nrm, int rs,
                                              const T* __restrict__ d, const int32_t* __restrict__ ids,
                                              const WChain<T>& chain, int k, int64_t N,
-                                             double* __restrict__ partials, const P4<T>* __restrict__ nbr = nullptr) {
+                                             double* __restrict__ partials, const P4<T>* __restrict__ nbr = nullptr,
+                                             const GDPred<T>& gdp = GDPred<T>{}) {
     constexpr int ST = P2PlaneSums<DIM, false>::kStats;  // (kSumW is the kept count with 0/1 weights)
     constexpr int NV = P2PlaneSums<DIM, false>::NV;
     double acc[NV];
@@ -180,7 +184,7 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
                 if (nbr) {
                     q[u] = nbr[jj];
                     n[u] = nbr[N + jj];
-                    if (SN) id[u] = ids[jj];
+                    if (SN || GD) id[u] = ids[jj];
                 } else {
                     id[u] = ids[jj];
                 }
@@ -201,11 +205,8 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (i0 + u * stride >= N) continue;
-                bool keep = chain_keep(wr, dv[u]);
-                if (SN) {
-                    keep = keep && id[u] >= 0 && sn_pass(chain.sn, Tm, rn[u], n[u]);
-                    kp[u] = kp[u] && keep;
-                }
+                const bool keep = pair_keep<T, SN, GD>(chain, gdp, wr, Tm, dv[u], id[u], rn[SN ? u : 0], n[u]);
+                if (SN || GD) kp[u] = kp[u] && keep;
                 if (keep) acc[ST + kNonzero] += 1.0;
                 if (dv[u] != inf && !keep) acc[ST + kRejMatches] += 1.0;
                 if (!kp[u]) {
@@ -252,8 +253,7 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
 #pragma unroll
             for (int s = 0; s < kGatherK; ++s) {
                 if (s >= k) continue;
-                bool keep = chain_keep(wr, dv[s]);
-                if (SN) keep = keep && id[s] >= 0 && sn_pass(chain.sn, Tm, rn, n[s]);
+                const bool keep = pair_keep<T, SN, GD>(chain, gdp, wr, Tm, dv[s], id[s], rn, n[s]);
                 if (keep) acc[ST + kNonzero] += 1.0;
                 if (dv[s] == inf) continue;
                 if (!keep) {
@@ -275,10 +275,14 @@ __device__ __forceinline__ void p2plane_body(const P4<T>* __restrict__ rd, const
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
             const T dv = d[e];
-            bool keep = chain_keep(wr,dv);
-            if (SN) {
+            bool keep = chain_keep(wr, dv);
+            if (SN || GD) {  // (the id and the records only for an entry the distances keep)
                 const int32_t id = ids[e];
-                keep = keep && id >= 0 && sn_pass(chain.sn, Tm, gld(chain.sn.rn, i), gld(nrm, (int64_t)id * rs));
+                if (keep && id >= 0)
+                    keep = pair_keep<T, SN, GD>(chain, gdp, wr, Tm, dv, id, SN ? gld(chain.sn.rn, i) : P4<T>{},
+                                                SN ? gld(nrm, (int64_t)id * rs) : P4<T>{});
+                else
+                    keep = false;
             }
             if (keep) acc[ST + kNonzero] += 1.0;
             if (dv == inf) continue;

@@ -30,15 +30,15 @@ namespace pmx {
 // only where the SurfaceNormal factor needs it (these kernels carry none
 // otherwise).  A robust point-to-plane distance is not evaluated here: its
 // weights come materialised (w_arr, every factor in them).
-template <typename T, bool SN>
+template <typename T, bool SN, bool GD = false>
 __device__ __forceinline__ T p2point_weight(const WChain<T>& chain, const SNPred<T>& sn, const WRange<T>& wr,
                                             const Mat4<T>& Tm, T dv, const T (&p)[3], int64_t i, int64_t e,
-                                            const int32_t* __restrict__ ids) {
+                                            const int32_t* __restrict__ ids, const GDPred<T>& gdp = GDPred<T>{}) {
     const auto inline_weight = [&]() {
-        const int32_t id = SN ? ids[e] : 0;
-        return entry_weight<T, SN, false>(
+        const int32_t id = SN || GD ? ids[e] : 0;
+        return entry_weight<T, SN, false, GD>(
             chain, sn, wr, Tm, dv, id, p[0], p[1], p[2], P4<T>{}, [&]() { return gld(sn.nrm, (int64_t)id * sn.rs); },
-            [&]() { return gld(sn.rn, i); });
+            [&]() { return gld(sn.rn, i); }, gdp);
     };
     // (the test of the array sits inside the robust side, where it was when the
     // SN = false kernels were tuned: they compile to the same instructions)
@@ -48,9 +48,15 @@ __device__ __forceinline__ T p2point_weight(const WChain<T>& chain, const SNPred
     };
     return chain.robust ? robust_side() : inline_weight();
 }
+// the launchers' choice among a kernel's instantiations (sn, gd: the chain
+// holds the SurfaceNormal / GenericDescriptor filter); chains without the
+// GenericDescriptor filter launch the GD = false ones, as before it existed
+#define PMX_PICK(sn, gd, K, ...)                                                         \
+    ((gd) ? ((sn) ? K<__VA_ARGS__, true, true> : K<__VA_ARGS__, false, true>) \
+          : ((sn) ? K<__VA_ARGS__, true, false> : K<__VA_ARGS__, false, false>))
 
 // (values: P2PlaneSums<DIM, false>, pmx_sums.h)
-template <typename T, int DIM, bool SN>
+template <typename T, int DIM, bool SN, bool GD>
 __global__ __launch_bounds__(256) void p2plane_partial_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                               const P4<T>* __restrict__ ref,
                                                               const P4<T>* __restrict__ nrm, int rs,
@@ -70,7 +76,9 @@ __global__ __launch_bounds__(256) void p2plane_partial_kernel(const P4<T>* __res
     }
     if (vzero && blockIdx.x == 0)  // (the spread counters the merged counter phase read, for the next match)
         for (int c = 0; c < 4; ++c) vzero[(size_t)(c * kVSlots + threadIdx.x) * kVStride] = 0ull;
-    p2plane_body<T, DIM, SN>(rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, nbr);
+    GDPred<T> gdp = chain.gd;  // (a copy: writing the kernel argument would move the chain to scratch)
+    if (GD) gd_bind(gdp, ctl, gd);
+    p2plane_body<T, DIM, SN, GD>(rd, Tm, ref, nrm, rs, d, ids, chain, k, N, partials, nbr, gdp);
 }
 
 // Real-valued weights (a RobustOutlierFilter in the chain; per-module path):
@@ -107,7 +115,7 @@ __device__ __forceinline__ void p2plane_add_full(double (&acc)[NV], T px, T py, 
         acc[L::kB + r] += (double)(wF * dot);
     }
 }
-template <typename T, int DIM, bool SN>
+template <typename T, int DIM, bool SN, bool GD>
 __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                                const P4<T>* __restrict__ ref,
                                                                const P4<T>* __restrict__ nrm, int rs,
@@ -125,6 +133,8 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
     }
     using L = P2PlaneSums<DIM, true>;
     constexpr int NV = L::NV;
+    GDPred<T> gdp = chain.gd;
+    if (GD) gd_bind(gdp, ctl, gd);
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -144,8 +154,8 @@ __global__ __launch_bounds__(256) void p2plane_weighted_kernel(const P4<T>* __re
                 q = gld(ref, (int64_t)id * rs);
                 n = gld(nrm, (int64_t)id * rs);
             }
-            const T w = entry_weight<T, SN>(chain, chain.sn, wr, Tm, dv, id, px, py, pz, q, loaded(n),
-                                            [&]() { return gld(chain.sn.rn, i); });
+            const T w = entry_weight<T, SN, true, GD>(chain, chain.sn, wr, Tm, dv, id, px, py, pz, q, loaded(n),
+                                                      [&]() { return gld(chain.sn.rn, i); }, gdp);
             if (!count_entry<L::kStats>(acc, w != (T)0, dv != inf)) continue;
             exist = true;
             acc[L::kStats + kSumW] += (double)w;
@@ -167,16 +177,17 @@ void launch_p2plane_partial(const MatchView<T>& m, const Mat4<T>& Tm, const WCha
                             double* partials, const LoopCtl* ctl, const GridDesc<T>* gd, unsigned long long* vzero,
                             hipStream_t s) {
     const bool sn = chain.sn.rn != nullptr;  // (the instantiations with the normal predicate)
-    if (chain.robust) {  // real-valued weights: the full asymmetric A (this kernel has no neighbour-record path)
-        auto* const kern = dim == 3 ? (sn ? p2plane_weighted_kernel<T, 3, true> : p2plane_weighted_kernel<T, 3, false>)
-                                    : (sn ? p2plane_weighted_kernel<T, 2, true> : p2plane_weighted_kernel<T, 2, false>);
+    const bool gdf = chain.gd.desc != nullptr;  // (and with the descriptor factor)
+    if (chain.real()) {  // real-valued weights: the full asymmetric A (this kernel has no neighbour-record path)
+        auto* const kern = dim == 3 ? PMX_PICK(sn, gdf, p2plane_weighted_kernel, T, 3)
+                                    : PMX_PICK(sn, gdf, p2plane_weighted_kernel, T, 2);
         hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k,
                            m.N, partials, ctl, gd);
         return;
     }
     // (m.nbr, k = 1: the kernel reads the records in slot order instead of gathering by id)
-    auto* const kern = dim == 3 ? (sn ? p2plane_partial_kernel<T, 3, true> : p2plane_partial_kernel<T, 3, false>)
-                                : (sn ? p2plane_partial_kernel<T, 2, true> : p2plane_partial_kernel<T, 2, false>);
+    auto* const kern = dim == 3 ? PMX_PICK(sn, gdf, p2plane_partial_kernel, T, 3)
+                                : PMX_PICK(sn, gdf, p2plane_partial_kernel, T, 2);
     hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k, m.N,
                        partials, ctl, gd, vzero, m.nbr);
 }
@@ -206,27 +217,29 @@ void launch_finalize(const double* partials, int nblocks, int nv, double* out, c
 // What the three kernels do first: in the device loop (ctl) the step transform,
 // the level's points and normals from the device.  sn: the caller's copy of chain.sn
 // (writing the kernel argument would move the chain to scratch).  False: the loop is done.
-template <typename T, bool SN>
+template <typename T, bool SN, bool GD>
 __device__ __forceinline__ bool p2point_begin(const LoopCtl* __restrict__ ctl, const GridDesc<T>* __restrict__ gd,
-                                              Mat4<T>& Tm, const P4<T>* __restrict__& ref, SNPred<T>& sn) {
+                                              Mat4<T>& Tm, const P4<T>* __restrict__& ref, SNPred<T>& sn,
+                                              GDPred<T>& gdp) {
     if (ctl) {
         if (ctl->done) return false;
         ctl_transform(ctl, Tm);
         ref = gd[ctl->level].gpts;
     }
     if (SN) sn_bind(sn, ctl, gd);
+    if (GD) gd_bind(gdp, ctl, gd);
     return true;
 }
 
 // pass 1: sum w, sum p*w, sum q*w (PointToPoint.cpp:67-72; with w = 1,
 // p * w == p exactly) + ErrorElements counts; RAW: the one-pass form's raw
 // moments sum (w q_r) p_c as well.  block: this block's place in the walk.
-template <typename T, bool SN, bool RAW>
+template <typename T, bool SN, bool RAW, bool GD>
 __device__ __forceinline__ void p2point_sums_body(const P4<T>* __restrict__ rd, const Mat4<T>& Tm,
                                                   const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                   const int32_t* __restrict__ ids, const WChain<T>& chain,
-                                                  const SNPred<T>& sn, int k, int64_t N, uint32_t block,
-                                                  double* __restrict__ partials) {
+                                                  const SNPred<T>& sn, const GDPred<T>& gdp, int k, int64_t N,
+                                                  uint32_t block, double* __restrict__ partials) {
     using L = P2PointSums;
     constexpr int NV = RAW ? L::kMomentsNV : L::kPass1NV;
     double acc[NV];
@@ -243,7 +256,7 @@ __device__ __forceinline__ void p2point_sums_body(const P4<T>* __restrict__ rd, 
             const int64_t e = i * k + s;
             const T dv = d[e];
             // 0/1 weights, or a robust chain's real weight (point2point distance)
-            const T w = p2point_weight<T, SN>(chain, sn, wr, Tm, dv, p, i, e, ids);
+            const T w = p2point_weight<T, SN, GD>(chain, sn, wr, Tm, dv, p, i, e, ids, gdp);
             if (!count_entry<L::kStats>(acc, w != (T)0, dv != inf)) continue;
             exist = true;
             const P4<T> q = gld(ref, ids[e]);
@@ -262,7 +275,7 @@ __device__ __forceinline__ void p2point_sums_body(const P4<T>* __restrict__ rd, 
     block_store<NV>(acc, partials);
 }
 
-template <typename T, bool SN>
+template <typename T, bool SN, bool GD>
 __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                             const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                             const int32_t* __restrict__ ids, WChain<T> chain, int k,
@@ -270,14 +283,15 @@ __global__ __launch_bounds__(256) void p2point_pass1_kernel(const P4<T>* __restr
                                                             const LoopCtl* __restrict__ ctl,
                                                             const GridDesc<T>* __restrict__ gd) {
     SNPred<T> sn = chain.sn;
-    if (!p2point_begin<T, SN>(ctl, gd, Tm, ref, sn)) return;
-    p2point_sums_body<T, SN, false>(rd, Tm, ref, d, ids, chain, sn, k, N, blockIdx.x, partials);
+    GDPred<T> gdp = chain.gd;
+    if (!p2point_begin<T, SN, GD>(ctl, gd, Tm, ref, sn, gdp)) return;
+    p2point_sums_body<T, SN, false, GD>(rd, Tm, ref, d, ids, chain, sn, gdp, k, N, blockIdx.x, partials);
 }
 
 template <typename T>
 void launch_p2point_pass1(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, double* partials,
                           const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s) {
-    auto* const kern = chain.sn.rn ? p2point_pass1_kernel<T, true> : p2point_pass1_kernel<T, false>;
+    auto* const kern = PMX_PICK(chain.sn.rn, chain.gd.desc, p2point_pass1_kernel, T);
     hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.ref, m.d, m.ids, chain, m.k, m.N, partials,
                        ctl, gd);
 }
@@ -304,7 +318,7 @@ void launch_p2point_means(const double* sums, T* means_dev, int dim, const LoopC
 // tenth sum, sigma = sum ||pc||^2 w (PointToPointSimilarity.cpp:69): each
 // pair's squared norm in T, (pcx pcx + pcy pcy) + pcz pcz, times w, added in
 // fp64.  The rigid minimiser's instantiations (SIM false) hold nine sums as before.
-template <typename T, bool SN, bool SIM>
+template <typename T, bool SIM, bool SN, bool GD>
 __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                             const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                             const int32_t* __restrict__ ids, WChain<T> chain, int k,
@@ -315,7 +329,8 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
     using L = P2PointSums;
     constexpr int NV = SIM ? L::kPass2SimNV : L::kPass2NV;
     SNPred<T> sn = chain.sn;
-    if (!p2point_begin<T, SN>(ctl, gd, Tm, ref, sn)) return;
+    GDPred<T> gdp = chain.gd;
+    if (!p2point_begin<T, SN, GD>(ctl, gd, Tm, ref, sn, gdp)) return;
     double acc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
@@ -330,7 +345,7 @@ __global__ __launch_bounds__(256) void p2point_pass2_kernel(const P4<T>* __restr
         for (int s = 0; s < k; ++s) {
             const int64_t e = i * k + s;
             const T dv = d[e];
-            const T w = p2point_weight<T, SN>(chain, sn, wr, Tm, dv, p, i, e, ids);
+            const T w = p2point_weight<T, SN, GD>(chain, sn, wr, Tm, dv, p, i, e, ids, gdp);
             if (dv == inf || w == (T)0) continue;
             const P4<T> q4 = gld(ref, ids[e]);
             const T q[3] = {q4.x, q4.y, q4.z};
@@ -356,8 +371,8 @@ template <typename T>
 void launch_p2point_pass2(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, const T* means_dev,
                           bool similarity, double* partials, const LoopCtl* ctl, const GridDesc<T>* gd,
                           hipStream_t s) {
-    auto* const kern = similarity ? (chain.sn.rn ? p2point_pass2_kernel<T, true, true> : p2point_pass2_kernel<T, false, true>)
-                                  : (chain.sn.rn ? p2point_pass2_kernel<T, true, false> : p2point_pass2_kernel<T, false, false>);
+    auto* const kern = similarity ? PMX_PICK(chain.sn.rn, chain.gd.desc, p2point_pass2_kernel, T, true)
+                                  : PMX_PICK(chain.sn.rn, chain.gd.desc, p2point_pass2_kernel, T, false);
     hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.ref, m.d, m.ids, chain, m.k, m.N, means_dev,
                        partials, ctl, gd);
 }
@@ -369,7 +384,7 @@ void launch_p2point_pass2(const MatchView<T>& m, const Mat4<T>& Tm, const WChain
 // fp64: sum w (q - mq)(p - mp)^T = sum (w q) p^T - mq (sum w p)^T
 // - (sum w q) mp^T + (sum w) mq mp^T (PointToPoint.cpp:67-81 by the same
 // identity; the two-pass kernels above are the per-module path's).
-template <typename T, bool SN>
+template <typename T, bool SN, bool GD>
 __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                               const P4<T>* __restrict__ ref, const T* __restrict__ d,
                                                               const int32_t* __restrict__ ids, WChain<T> chain, int k,
@@ -377,14 +392,15 @@ __global__ __launch_bounds__(256) void p2point_moments_kernel(const P4<T>* __res
                                                               const LoopCtl* __restrict__ ctl,
                                                               const GridDesc<T>* __restrict__ gd) {
     SNPred<T> sn = chain.sn;
-    if (!p2point_begin<T, SN>(ctl, gd, Tm, ref, sn)) return;
-    p2point_sums_body<T, SN, true>(rd, Tm, ref, d, ids, chain, sn, k, N, xcd_block(), partials);
+    GDPred<T> gdp = chain.gd;
+    if (!p2point_begin<T, SN, GD>(ctl, gd, Tm, ref, sn, gdp)) return;
+    p2point_sums_body<T, SN, true, GD>(rd, Tm, ref, d, ids, chain, sn, gdp, k, N, xcd_block(), partials);
 }
 
 template <typename T>
 void launch_p2point_moments(const MatchView<T>& m, const Mat4<T>& Tm, const WChain<T>& chain, double* partials,
                             const LoopCtl* ctl, const GridDesc<T>* gd, hipStream_t s) {
-    auto* const kern = chain.sn.rn ? p2point_moments_kernel<T, true> : p2point_moments_kernel<T, false>;
+    auto* const kern = PMX_PICK(chain.sn.rn, chain.gd.desc, p2point_moments_kernel, T);
     hipLaunchKernelGGL(kern, dim3(kRedBlocks), dim3(256), 0, s, m.rd, Tm, m.ref, m.d, m.ids, chain, m.k, m.N, partials,
                        ctl, gd);
 }
@@ -395,7 +411,7 @@ void launch_p2point_moments(const MatchView<T>& m, const Mat4<T>& Tm, const WCha
 // needs the step reading and the matched point and normal; the SurfaceNormal
 // factor the matched normal, which at k = 1 comes from the match's neighbour
 // record when there is one (nbr_n, slot order, no dependent gather).
-template <typename T, bool SN>
+template <typename T, bool SN, bool GD>
 __global__ __launch_bounds__(256) void weights_chain_kernel(const P4<T>* __restrict__ rd, Mat4<T> Tm,
                                                             const P4<T>* __restrict__ ref,
                                                             const P4<T>* __restrict__ nrm, int rs,
@@ -407,10 +423,10 @@ __global__ __launch_bounds__(256) void weights_chain_kernel(const P4<T>* __restr
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
         const int64_t i = k == 1 ? e : e / k;
-        const int32_t id = SN || p2pl ? ids[e] : -1;
+        const int32_t id = SN || GD || p2pl ? ids[e] : -1;
         T px = 0, py = 0, pz = 0;
         P4<T> q{}, qn{};
-        if (id >= 0) {
+        if (id >= 0 && (!GD || SN || p2pl)) {  // (the descriptor factor alone reads no record)
             const int64_t g = (int64_t)id * rs;
             qn = nbr_n ? gld(nbr_n, i) : gld(nrm, g);
             if (p2pl) {
@@ -418,8 +434,8 @@ __global__ __launch_bounds__(256) void weights_chain_kernel(const P4<T>* __restr
                 xform3(Tm, rd[i], px, py, pz);
             }
         }
-        w[e] = entry_weight<T, SN>(chain, chain.sn, wr, Tm, d[e], id, px, py, pz, q, loaded(qn),
-                                   [&]() { return gld(chain.sn.rn, i); });
+        w[e] = entry_weight<T, SN, true, GD>(chain, chain.sn, wr, Tm, d[e], id, px, py, pz, q, loaded(qn),
+                                             [&]() { return gld(chain.sn.rn, i); }, chain.gd);
     }
 }
 template <typename T>
@@ -428,7 +444,7 @@ void launch_weights_chain(const MatchView<T>& m, const Mat4<T>& Tm, const WChain
     if (n <= 0) return;
     int64_t g = (n + 1023) / 1024;
     if (g > 4096) g = 4096;
-    auto* const kern = chain.sn.rn ? weights_chain_kernel<T, true> : weights_chain_kernel<T, false>;
+    auto* const kern = PMX_PICK(chain.sn.rn, chain.gd.desc, weights_chain_kernel, T);
     hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), 0, s, m.rd, Tm, m.pn, m.nrm, m.rs, m.d, m.ids, chain, m.k, n,
                        m.nbr ? m.nbr + m.N : nullptr, w);
 }

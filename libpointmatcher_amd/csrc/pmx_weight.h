@@ -17,12 +17,18 @@
 // the matched reference point's normals (SNPred, sn_pass).  The reductions
 // evaluate it in instantiations of their own, selected at launch when the
 // chain holds it.
+// The GenericDescriptorOutlierFilter (OutlierFiltersImpl.cpp:290-374) reads no
+// distance either (kWPGeneric): its weight comes from a one-row descriptor of
+// the matched reference point (GDPred, gd_weight).  Its hard form is a 0/1
+// predicate (the exact path, in instantiations of their own as SurfaceNormal's),
+// its soft form the second filter with real-valued weights (the weighted path).
 // entry_weight (below) is the one statement of the product.
 #pragma once
 
 namespace pmx {
 
-enum WPred { kWPDefault = 0, kWPNull = 1, kWPLe = 2, kWPGe = 3, kWPState = 4, kWPRobust = 5, kWPNormal = 6 };
+enum WPred { kWPDefault = 0, kWPNull = 1, kWPLe = 2, kWPGe = 3, kWPState = 4, kWPRobust = 5, kWPNormal = 6,
+             kWPGeneric = 7 };
 // rn != null: the filter is in the chain and both clouds carry normals.
 template <typename T>
 struct SNPred {
@@ -31,6 +37,18 @@ struct SNPred {
     int rs = 1;                 // their index stride (2: a grid level's interleaved records)
     int dim = 3;
     T eps = 0;                  // cos(maxAngle) in T (several filters: the largest)
+};
+// GenericDescriptorOutlierFilter.  desc != null: the filter is in the chain.
+// desc holds one value per reference point in the order of the match ids (a
+// grid level's permuted copy after a grid match, GridDesc::gw; the uploaded
+// array after a brute-force match), so a pair costs one gather.
+enum GDMode { kGDSoft = 0, kGDLess = 1, kGDGreater = 2 };
+template <typename T>
+struct GDPred {
+    const T* desc = nullptr;
+    int mode = kGDSoft;
+    T thr = 0;                  // hard modes: the threshold in T
+    const double* m = nullptr;  // soft: the maximum over all k x N entries (device, a T value; gd_max_kernel)
 };
 enum RobustFct { kRFCauchy = 0, kRFWelsch = 1, kRFSC = 2, kRFGM = 3, kRFTukey = 4, kRFHuber = 5, kRFL1 = 6,
                  kRFStudent = 7 };
@@ -51,6 +69,9 @@ struct WChain {
     int rb_p2pl = 0;
     const T* w_arr = nullptr;  // materialised weights (a robust point-to-plane distance, point-to-point minimiser)
     SNPred<T> sn;              // kWPNormal
+    GDPred<T> gd;              // kWPGeneric
+    // real-valued weights: the reductions take the weighted path
+    __host__ __device__ bool real() const { return robust != 0 || (gd.desc != nullptr && gd.mode == kGDSoft); }
 };
 // robustFiltering's weight of one scaled squared error (OutlierFiltersImpl.cpp:541-596)
 template <typename T>
@@ -179,6 +200,45 @@ __device__ __forceinline__ bool sn_pass(const SNPred<T>& p, const Mat4<T>& Tm, c
     return !(a < p.eps);
 }
 
+// ---- the GenericDescriptorOutlierFilter's per-pair factor ----
+// device loop: the descriptor copy of this iteration's grid level
+template <typename T>
+__device__ __forceinline__ void gd_bind(GDPred<T>& p, const LoopCtl* ctl, const GridDesc<T>* gd) {
+    if (ctl) p.desc = gd[ctl->level].gw;
+}
+// one scalar gather through an explicitly global pointer (see gld)
+template <typename T>
+__device__ __forceinline__ T gd_load(const T* p, int64_t i) {
+    return ((const __attribute__((address_space(1))) T*)p)[i];
+}
+// the hard forms (OutlierFiltersImpl.cpp:343-354): both comparisons strict, in T
+template <typename T>
+__device__ __forceinline__ bool gd_pass(const GDPred<T>& p, int32_t id) {
+    const T v = gd_load(p.desc, id);
+    return p.mode == kGDGreater ? v > p.thr : v < p.thr;
+}
+// The filter's weight of a pair: no neighbour gives 0; hard 0/1; soft
+// desc[id], then every entry divided (a true division in T) by the maximum m
+// over all entries, the zeros of the entries without a neighbour included
+// (OutlierFiltersImpl.cpp:334-371).  m <= 0 is not guarded: IEEE decides.
+template <typename T>
+__device__ __forceinline__ T gd_weight(const GDPred<T>& p, int32_t id) {
+    if (p.mode == kGDSoft) return (id >= 0 ? gd_load(p.desc, id) : (T)0) / (T)*p.m;
+    return id >= 0 && gd_pass(p, id) ? (T)1 : (T)0;
+}
+
+// A chain of 0/1 factors only keeps the pair (entry_weight != 0 there): the
+// distance predicates, then each id-reading predicate of a valid id.  The
+// point-to-plane body evaluates it in this form around its own order of loads.
+template <typename T, bool SN, bool GD>
+__device__ __forceinline__ bool pair_keep(const WChain<T>& c, const GDPred<T>& gd, const WRange<T>& wr,
+                                          const Mat4<T>& Tm, T dv, int32_t id, const P4<T>& rn, const P4<T>& n) {
+    bool keep = chain_keep(wr, dv);
+    if (SN) keep = keep && id >= 0 && sn_pass(c.sn, Tm, rn, n);
+    if (GD) keep = keep && id >= 0 && gd_pass(gd, id);
+    return keep;
+}
+
 // ---- the weight of one match entry ----
 // a value the caller has loaded, in the callable form entry_weight takes
 template <typename V>
@@ -189,15 +249,23 @@ __device__ __forceinline__ auto loaded(const V& v) {
 // The chain's weight of the entry (distance dv, reference id) of the reading
 // point whose step point is p, in the reference's order of the product
 // (OutlierFilter.cpp:63-103):
-//   w    = pred(dv) * robust(dist / s^2) * sn
+//   w    = pred(dv) * robust(dist / s^2) * sn * gd
 //   pred = the distance predicates' 0/1 (wr: chain_resolve of the chain)
 //   dist = rb_p2pl ? (id >= 0 ? p2pl_distance(p, q, n) : 0) : dv
 //          (the predicates judge the match distance, the robust function the
 //          chosen one; 0 for an invalid match, OutlierFiltersImpl.cpp:460-489);
 //          s the chain's scale in T
 //   sn   = id >= 0 && sn_pass(rn, n)
+//   gd   = gd_weight(id): 0/1 (hard), or (id >= 0 ? desc[id] : 0) / m (soft)
 // The robust factor is absent for a chain without the filter, the SurfaceNormal
-// factor when SN is false (sn: the caller's SNPred, chain.sn or a bound copy).
+// factor when SN is false (sn: the caller's SNPred, chain.sn or a bound copy),
+// the GenericDescriptor factor when GD is false (gd: likewise, chain.gd or bound).
+// At most one RobustOutlierFilter and one GenericDescriptorOutlierFilter per
+// chain: with at most two real-valued factors (robust, soft gd) and 0/1
+// factors otherwise, the product in T is the same in every order (a product of
+// two T values commutes, and a 0/1 factor is exact wherever it stands), so the
+// fixed order here gives the reference's bits for any chain order.  A third
+// real-valued factor would make the rounding depend on the order.
 // P2PL false: the caller's chains never ask for the point-to-plane distance
 // (p, q and the normal are then not read for it).
 // q: the matched reference point as loaded (anything for id < 0).  n, rn: the
@@ -206,14 +274,18 @@ __device__ __forceinline__ auto loaded(const V& v) {
 // the normal for the point-to-plane distance of a valid id, both for the
 // SurfaceNormal factor of a valid id whose weight is non-zero so far.
 // Skipping that factor at w == 0 changes no bit: +0 * (0|1) == +0.
+// The hard GenericDescriptor factor is skipped likewise, by the same argument
+// (w is +0 or non-zero there, the factor 0 or 1).  The soft factor is always
+// formed: 0 * (desc / m) is -0 for a negative quotient and NaN for an
+// infinite one, which a skip would lose.
 // NaN: pred * robust is always formed, so a NaN scale or a NaN / infinite
 // robust value gives a NaN weight even at pred == 0, and NaN != 0 counts as a
 // non-zero weight everywhere, as Eigen's (w != 0) does.  A zero normal passes
 // the SurfaceNormal factor (sn_pass).
-template <typename T, bool SN, bool P2PL = true, typename QN, typename RN>
+template <typename T, bool SN, bool P2PL = true, bool GD = false, typename QN, typename RN>
 __device__ __forceinline__ T entry_weight(const WChain<T>& c, const SNPred<T>& sn, const WRange<T>& wr,
                                           const Mat4<T>& Tm, T dv, int32_t id, T px, T py, T pz, const P4<T>& q,
-                                          QN&& n, RN&& rn) {
+                                          QN&& n, RN&& rn, const GDPred<T>& gd = GDPred<T>{}) {
     T w;
     if (c.robust) {
         T dist = dv;
@@ -225,6 +297,7 @@ __device__ __forceinline__ T entry_weight(const WChain<T>& c, const SNPred<T>& s
         w = chain_keep(wr, dv) ? (T)1 : (T)0;
     }
     if (SN && w != (T)0) w = w * (id >= 0 && sn_pass(sn, Tm, rn(), n()) ? (T)1 : (T)0);
+    if (GD && (gd.mode == kGDSoft || w != (T)0)) w = w * gd_weight(gd, id);
     return w;
 }
 

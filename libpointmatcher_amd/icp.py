@@ -74,6 +74,7 @@ def lib():
         l.pmx_icp_comm_init_host.argtypes = [C.c_void_p, C.c_int, C.c_int, _capi.ALLREDUCE_FN, _capi.ALLGATHER_FN,
                                              C.c_void_p]
         l.pmx_icp_keep_trace.argtypes = [C.c_void_p, C.c_int]
+        l.pmx_icp_outlier_filter_doc.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int]
         l.pmx_icp_add_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_int64]
         l.pmx_cloud_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         l.pmx_cloud_destroy.argtypes = [C.c_void_p]
@@ -109,6 +110,17 @@ def lib():
         l.pmx_icp_sequence_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
+
+
+def outlier_filter_doc(name, dtype=np.float32):
+    """The parameter documentation of a registered outlier filter, as the
+    reference prints a Parametrizable (one "- name (default: v) - doc - min: a -
+    max: b" line per parameter)."""
+    buf = C.create_string_buffer(8192)
+    rc = lib().pmx_icp_outlier_filter_doc(1 if np.dtype(dtype) == np.float64 else 0, name.encode(), buf, len(buf))
+    if rc:
+        raise _ERR.get(rc, RuntimeError)(f"no documentation for outlier filter {name}")
+    return buf.value.decode()
 
 
 def _p(a):
