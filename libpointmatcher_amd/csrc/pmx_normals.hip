@@ -5,8 +5,8 @@
 // KDTreeMatcher with ALLOW_SELF_MATCH, SurfaceNormal.cpp:158-162,
 // MatchersImpl.cpp:98) come from the exact grid matcher; this kernel does the
 // per-point statistics, one lane per point:
-//   mean of the valid neighbours and the centred set NN in T
-//                                                  (SurfaceNormal.cpp:170-181)
+//   mean of the valid neighbours and the centred set NN in T, both taken
+//     relative to the point itself             (SurfaceNormal.cpp:170-181)
 //   C = NN NN^T in T, sequential over the neighbours (:183)
 //   the rank test C.fullPivHouseholderQr().rank() + 1 >= D (:188), with the
 //     restated FullPivHouseholderQR of common/pmx_dense.h
@@ -130,7 +130,13 @@ __global__ __launch_bounds__(256) void surface_normals_kernel(
     bool degen = false;
     if (s < N) {
         const T inf = (T)__builtin_huge_val();
-        // mean of the valid neighbours (d.rowwise().sum() / realKnn)
+        // Every statistic is taken on the neighbours relative to the point
+        // itself, q_j - p (exact in T for near neighbours): C, the eigen pairs,
+        // the density and |p - mean| are translation invariant, and summing
+        // absolute coordinates in T (the reference's d.rowwise().sum()) loses
+        // them to cancellation on a small cloud far from the origin.
+        const P4<T> self = pts[s];
+        // mean of the valid neighbours (d.rowwise().sum() / realKnn), relative to p
         T sum[D];
 #pragma unroll
         for (int r = 0; r < D; ++r) sum[r] = 0;
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(256) void surface_normals_kernel(
             if (dists[s * k + j] == inf) continue;
             const P4<T> p = gld32(gpts, (uint32_t)ids[s * k + j]);
 #pragma unroll
-            for (int r = 0; r < D; ++r) sum[r] = sum[r] + coord(p, r);
+            for (int r = 0; r < D; ++r) sum[r] = sum[r] + (coord(p, r) - coord(self, r));
             ++real;
         }
         T mean[D];
@@ -157,7 +163,7 @@ __global__ __launch_bounds__(256) void surface_normals_kernel(
             T n2 = 0;
 #pragma unroll
             for (int r = 0; r < D; ++r) {
-                nn[r] = coord(p, r) - mean[r];
+                nn[r] = (coord(p, r) - coord(self, r)) - mean[r];
                 n2 = n2 + nn[r] * nn[r];
             }
 #pragma unroll
@@ -224,13 +230,9 @@ __global__ __launch_bounds__(256) void surface_normals_kernel(
             if (degen) {
                 md = (T)18446744073709551615.0;  // std::numeric_limits<std::size_t>::max()
             } else {
-                const P4<T> p = pts[s];
-                T n2 = 0;
+                T n2 = 0;  // |p - mean|: the relative mean's own length
 #pragma unroll
-                for (int r = 0; r < D; ++r) {
-                    const T d = coord(p, r) - mean[r];
-                    n2 = n2 + d * d;
-                }
+                for (int r = 0; r < D; ++r) n2 = n2 + mean[r] * mean[r];
                 md = sqrt(n2);
             }
             o_mdist[s] = md;

@@ -964,7 +964,9 @@ int SUF(pmo_surface_normals)(const T* pts, int rows, int64_t n, int k, T maxDist
         for (int j = 0; j < k; ++j) {
             if (dd[i * k + j] == (T)INFINITY) continue;
             const T* p = pts + (int64_t)ii[i * k + j] * rows;
-            for (int r = 0; r < D; ++r) sum[r] = sum[r] + p[r];
+            /* relative to the point itself (pmx_normals.hip: translation invariant,
+             * no cancellation on a small cloud far from the origin) */
+            for (int r = 0; r < D; ++r) sum[r] = sum[r] + (p[r] - pts[i * rows + r]);
             ++real;
         }
         T mean[3];
@@ -977,7 +979,7 @@ int SUF(pmo_surface_normals)(const T* pts, int rows, int64_t n, int k, T maxDist
             T nn[3];
             T n2 = 0;
             for (int r = 0; r < D; ++r) {
-                nn[r] = p[r] - mean[r];
+                nn[r] = (p[r] - pts[i * rows + r]) - mean[r];
                 n2 = n2 + nn[r] * nn[r];
             }
             for (int a = 0; a < D; ++a)
@@ -1018,10 +1020,7 @@ int SUF(pmo_surface_normals)(const T* pts, int rows, int64_t n, int k, T maxDist
                 mdist[i] = (T)18446744073709551615.0;
             } else {
                 T n2 = 0;
-                for (int r = 0; r < D; ++r) {
-                    const T d = pts[i * rows + r] - mean[r];
-                    n2 = n2 + d * d;
-                }
+                for (int r = 0; r < D; ++r) n2 = n2 + mean[r] * mean[r];
                 mdist[i] = (T)sqrt((double)n2);
             }
         }
