@@ -588,6 +588,39 @@ int pmx_voxel_grid(int device, int dtype, const void* feat, int rows, int64_t n,
                    const double* vsize, int use_centroid, int average_desc, void* feat_out, void* desc_out,
                    int64_t* n_out);
 
+/* The keep-filters: a per-point predicate, then a stable compaction of whole
+ * feature and descriptor columns — the loops of
+ *   PMX_KEEP_SHADOW          ShadowDataPointsFilter (DataPointsFilters/Shadow.cpp:62-94):
+ *                            keep |normalized(n) . normalized(p)| > value, value =
+ *                            sin(eps) computed by the caller in T; index = the row
+ *                            offset of "normals" (span D) in desc; normalized()
+ *                            leaves a zero vector as it is (Eigen 3.3)
+ *   PMX_KEEP_MAX_QUANTILE    MaxQuantileOnAxisDataPointsFilter
+ *                            (DataPointsFilters/MaxQuantileOnAxis.cpp:65-98): keep
+ *                            feat[index] < limit, limit the element of rank
+ *                            size_t(n * value) of that row (value = ratio, the
+ *                            product in T), found by an exact radix select; strict,
+ *                            so the points tied with the limit are dropped
+ *   PMX_KEEP_REMOVE_NAN      RemoveNaNDataPointsFilter (DataPointsFilters/RemoveNaN.cpp:
+ *                            47-66): keep the points without a NaN in any feature
+ *                            row, the homogeneous one included
+ *   PMX_KEEP_CUT_DESCRIPTOR  CutAtDescriptorThresholdDataPointsFilter
+ *                            (DataPointsFilters/CutAtDescriptorThreshold.cpp:61-102):
+ *                            v = desc[index]; keep v <= value when flag
+ *                            (useLargerThan: the larger ones are cut), else v >= value
+ * Every predicate is evaluated in T in the reference's operation order,
+ * multiplies and adds rounded separately.  The kept points come out in their
+ * input order (two passes and a scan, no atomics: deterministic);
+ * feat_out / desc_out hold n points.  n = 0 and a kept count of 0 are results,
+ * not errors.  PMX_E_BAD_PARAM for rows other than 3 or 4, an unknown
+ * predicate, an index that is not a row of the features (MAX_QUANTILE) or of
+ * desc (SHADOW: index + D rows; CUT_DESCRIPTOR).  Standalone like
+ * pmx_voxel_grid; pmx_last_error(NULL) on failure. */
+enum { PMX_KEEP_SHADOW = 0, PMX_KEEP_MAX_QUANTILE = 1, PMX_KEEP_REMOVE_NAN = 2, PMX_KEEP_CUT_DESCRIPTOR = 3 };
+int pmx_keep_filter(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc, int desc_dim,
+                    int predicate, int index, int flag, double value, void* feat_out, void* desc_out,
+                    int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

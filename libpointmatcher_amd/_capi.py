@@ -171,7 +171,7 @@ EXPORTS = [
     "pmx_p2plane_system", "pmx_p2plane_system_forced", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
-    "pmx_sampling_surface_normals", "pmx_voxel_grid",
+    "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter",
 ]
 
 
@@ -246,6 +246,8 @@ def lib():
         l.pmx_voxel_grid.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
                                      C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int64)]
+        l.pmx_keep_filter.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         l.pmx_sampling_surface_normals.argtypes = ([C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint]
                                                    + [C.c_void_p] * 6 + [C.POINTER(C.c_int64)] * 2)
@@ -348,6 +350,37 @@ def voxel_grid(points, descriptors=None, vsize=(1.0, 1.0, 1.0), use_centroid=Tru
     rc = l.pmx_voxel_grid(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n, _ptr(desc), dd,
                           vs, 1 if use_centroid else 0, 1 if average_descriptors else 0, _ptr(of),
                           _ptr(od) if dd else None, C.byref(no))
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    return of[:no.value], od[:no.value]
+
+
+KEEP_SHADOW, KEEP_MAX_QUANTILE, KEEP_REMOVE_NAN, KEEP_CUT_DESCRIPTOR = range(4)  # PMX_KEEP_*
+
+
+def keep_filter(points, descriptors, predicate, index=0, flag=0, value=0.0, device=0):
+    """The keep-filters on the GPU (pmx_keep_filter, pmx_keep.hip): Shadow
+    (Shadow.cpp:62-94; index = row offset of the normals in descriptors, value
+    = sin(eps) in the cloud's type), MaxQuantileOnAxis (MaxQuantileOnAxis.cpp:
+    65-98; index = dim, value = ratio), RemoveNaN (RemoveNaN.cpp:47-66) and
+    CutAtDescriptorThreshold (CutAtDescriptorThreshold.cpp:61-102; index =
+    descriptor row, flag = useLargerThan, value = threshold).  points (n, rows)
+    with the homogeneous row last; descriptors (n, desc_dim) or None.  Returns
+    (features, descriptors) of the kept points, in their input order."""
+    pts = np.ascontiguousarray(points)
+    if pts.dtype not in (np.float32, np.float64):
+        pts = pts.astype(np.float32)
+    dt = pts.dtype
+    n, rows = pts.shape
+    dd = 0 if descriptors is None else descriptors.shape[1]
+    desc = None if descriptors is None else np.ascontiguousarray(descriptors, dtype=dt)
+    of = np.empty((n, rows), dt)
+    od = np.empty((n, dd), dt)
+    no = C.c_int64(0)
+    l = lib()
+    rc = l.pmx_keep_filter(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n,
+                           _ptr(desc) if dd else None, dd, int(predicate), int(index), int(flag), float(value),
+                           _ptr(of), _ptr(od) if dd else None, C.byref(no))
     if rc != PMX_OK:
         raise_for(rc, l.pmx_last_error(None).decode())
     return of[:no.value], od[:no.value]

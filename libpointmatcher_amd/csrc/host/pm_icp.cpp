@@ -1363,6 +1363,230 @@ struct VoxelGridDPF : PM<T>::DataPointsFilter {
     }
 };
 
+// The keep-filters on the device (pmx_keep_filter, pmx_keep.hip): a per-point
+// predicate and a stable compaction of features and descriptors.
+template <typename T>
+void keep_on_device(DataPoints<T>& cloud, int device, const char* who, int pred, int index, int flag, double value) {
+    cloud.materialize();
+    const int64_t n = cloud.n;
+    std::vector<T> feat((size_t)(n * cloud.rows)), desc((size_t)(n * cloud.descDim));
+    int64_t nout = 0;
+    const int rc = pmx_keep_filter(device, dtype_of<T>(), cloud.features.data(), cloud.rows, n,
+                                   cloud.descDim ? cloud.descriptors.data() : nullptr, cloud.descDim, pred, index, flag,
+                                   value, feat.data(), cloud.descDim ? desc.data() : nullptr, &nout);
+    if (rc == PMX_E_BAD_PARAM) throw InvalidParameter(pmx_last_error(nullptr));
+    if (rc) throw std::runtime_error(std::string(who) + ": " + pmx_last_error(nullptr));
+    cloud.n = nout;
+    feat.resize((size_t)(nout * cloud.rows));
+    cloud.features.swap(feat);
+    desc.resize((size_t)(nout * cloud.descDim));
+    cloud.descriptors.swap(desc);
+}
+
+// row offset and span of a descriptor; false when the cloud has none of that name
+template <typename T>
+bool descriptor_rows(const DataPoints<T>& cloud, const std::string& name, int& off, int& span) {
+    off = 0;
+    for (auto& l : cloud.descriptorLabels) {
+        if (l.text == name) {
+            span = l.span;
+            return true;
+        }
+        off += l.span;
+    }
+    return false;
+}
+
+// ShadowDataPointsFilter (DataPointsFilters/Shadow.cpp:44-94, parameter
+// Shadow.h:60-65): keep |normalized(normal) . normalized(point)| > sin(eps);
+// the constructor takes the sine in T.
+template <typename T>
+struct ShadowDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("eps", "Small angle (in rad) around which a normal shoudn't be observable", "0.1", "0.0", "3.1416",
+                     &P::Comp<T>)};
+    }
+    const T eps;  // sin(eps)
+    explicit ShadowDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("ShadowDataPointsFilter", doc(), p), eps(std::sin(this->template get<T>("eps"))) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        int off = 0, span = 0;
+        if (!descriptor_rows(cloud, "normals", off, span))
+            throw InvalidField("ShadowDataPointsFilter, Error: cannot find normals in descriptors");
+        if (span != cloud.rows - 1)  // (an Eigen size assertion in the reference's dot)
+            throw InvalidField("ShadowDataPointsFilter: normals and points differ in rows");
+        keep_on_device(cloud, this->device, "ShadowDataPointsFilter", PMX_KEEP_SHADOW, off, 0, (double)eps);
+    }
+};
+
+// MaxQuantileOnAxisDataPointsFilter (DataPointsFilters/MaxQuantileOnAxis.cpp:
+// 44-98, parameters MaxQuantileOnAxis.h:56-62): keep feature[dim] < limit,
+// limit the element of rank size_t(n * ratio); strict, so an axis of equal
+// values gives an empty cloud.  An empty cloud is left as it is (the reference
+// reads past an empty vector).
+template <typename T>
+struct MaxQuantileOnAxisDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("dim", "dimension on which the filter will be applied. x=0, y=1, z=2", "0", "0", "2",
+                     &P::Comp<unsigned>),
+                PDoc("ratio", "maximum quantile authorized. All points beyond that will be filtered.", "0.5",
+                     "0.0000001", "0.9999999", &P::Comp<T>)};
+    }
+    const unsigned dim;
+    const T ratio;
+    explicit MaxQuantileOnAxisDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("MaxQuantileOnAxisDataPointsFilter", doc(), p),
+          dim(this->template get<unsigned>("dim")),
+          ratio(this->template get<T>("ratio")) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        if ((int)dim >= cloud.rows)
+            throw InvalidParameter("MaxQuantileOnAxisDataPointsFilter: Error, filtering on dimension number " +
+                                   std::to_string(dim) + ", larger than feature dimensionality " +
+                                   std::to_string(cloud.rows));
+        keep_on_device(cloud, this->device, "MaxQuantileOnAxisDataPointsFilter", PMX_KEEP_MAX_QUANTILE, (int)dim, 0,
+                       (double)ratio);
+    }
+};
+
+// RemoveNaNDataPointsFilter (DataPointsFilters/RemoveNaN.cpp:47-66; no
+// parameter): drop the points with a NaN in any feature row.
+template <typename T>
+struct RemoveNaNDPF : PM<T>::DataPointsFilter {
+    explicit RemoveNaNDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("RemoveNaNDataPointsFilter", Parametrizable::ParametersDoc(), p) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        keep_on_device(cloud, this->device, "RemoveNaNDataPointsFilter", PMX_KEEP_REMOVE_NAN, 0, 0, 0.0);
+    }
+};
+
+// CutAtDescriptorThresholdDataPointsFilter (DataPointsFilters/
+// CutAtDescriptorThreshold.cpp:41-102, parameters CutAtDescriptorThreshold.h:
+// 62-68): the first row of descName against the threshold; useLargerThan cuts
+// the larger values (keep <=), else the smaller ones (keep >=).
+template <typename T>
+struct CutAtDescriptorThresholdDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("descName", "Descriptor name used to cut points", "none"),
+                PDoc("useLargerThan",
+                     "If set to 1 (true), points with values above the 'threshold' will be cut.  If set to 0 (false), "
+                     "points with values below the 'threshold' will be cut.",
+                     "1", "0", "1", &P::Comp<bool>),
+                PDoc("threshold", "Value at which to cut.", "0", "-inf", "inf", &P::Comp<T>)};
+    }
+    const std::string descName;
+    const bool useLargerThan;
+    const T threshold;
+    explicit CutAtDescriptorThresholdDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("CutAtDescriptorThresholdDataPointsFilter", doc(), p),
+          descName(this->template get<std::string>("descName")),
+          useLargerThan(this->template get<bool>("useLargerThan")),
+          threshold(this->template get<T>("threshold")) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        int off = 0, span = 0;
+        if (!descriptor_rows(cloud, descName, off, span))
+            throw InvalidField("CutAtDescriptorThresholdDataPointsFilter: Error, field not found in descriptors.");
+        keep_on_device(cloud, this->device, "CutAtDescriptorThresholdDataPointsFilter", PMX_KEEP_CUT_DESCRIPTOR, off,
+                       useLargerThan ? 1 : 0, (double)threshold);
+    }
+};
+
+// MaxDensityDataPointsFilter (DataPointsFilters/MaxDensity.cpp:44-105,
+// parameter MaxDensity.h:57-62): a point denser than maxDensity is kept when
+// (float)rand() / RAND_MAX < maxDensity / density, one draw per such point in
+// order — host code on the process's rand() state, like RandomSampling.  The
+// saturation term is restated as written: nbSaturatedPts / nbPointsIn is an
+// integer division, 0 unless every point has the maximum density (then the
+// ratio of those points is 0 and none passes).
+template <typename T>
+struct MaxDensityDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("maxDensity", "Maximum density of points to target. Unit: number of points per m^3.", "10",
+                     "0.0000001", "inf", &P::Comp<T>)};
+    }
+    const T maxDensity;
+    explicit MaxDensityDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("MaxDensityDataPointsFilter", doc(), p),
+          maxDensity(this->template get<T>("maxDensity")) {}
+    bool usesRandState() const override { return true; }
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        int off = 0, span = 0;
+        if (!descriptor_rows(cloud, "densities", off, span))
+            throw InvalidField("MaxDensityDataPointsFilter: Error, no densities found in descriptors.");
+        cloud.materialize();
+        const int nbPointsIn = (int)cloud.n;
+        if (nbPointsIn == 0) return;  // (maxCoeff of an empty view in the reference)
+        const int dd = cloud.descDim;
+        // maxCoeff / count over the whole view (span rows; densities has one)
+        T lastDensity = cloud.descriptors[(size_t)off];
+        for (int64_t i = 0; i < cloud.n; ++i)
+            for (int r = 0; r < span; ++r) {
+                const T v = cloud.descriptors[(size_t)i * dd + off + r];
+                if (v > lastDensity) lastDensity = v;
+            }
+        int nbSaturatedPts = 0;
+        for (int64_t i = 0; i < cloud.n; ++i)
+            for (int r = 0; r < span; ++r)
+                nbSaturatedPts += cloud.descriptors[(size_t)i * dd + off + r] == lastDensity ? 1 : 0;
+        int64_t i = -1;
+        compact_points(cloud, [&](const T*) {
+            ++i;
+            const T density = cloud.descriptors[(size_t)i * dd + off];
+            if (!(density > maxDensity)) return true;
+            const float r = (float)std::rand() / (float)RAND_MAX;
+            float acceptRatio = maxDensity / density;
+            if (density == lastDensity) acceptRatio = acceptRatio * (1 - nbSaturatedPts / nbPointsIn);
+            return r < acceptRatio;
+        });
+    }
+};
+
+// MaxPointCountDataPointsFilter (DataPointsFilters/MaxPointCount.cpp:41-102,
+// parameters MaxPointCount.h:56-63): with maxCount <= N = n - 1, srand(seed) on
+// every call, then for j < maxCount an index idx = j + size_t((N - j) *
+// float(rand() / float(RAND_MAX))) and the reference's "switch" of columns j
+// and idx — whose temporary is a view of column j, not a copy, so column j
+// takes column idx and column idx keeps its value (a sample with repetition,
+// not a shuffle).  Restated as the code runs, descriptors alike; the first
+// maxCount columns stay.  maxCount > N: nothing happens.  (seed and maxCount
+// are size_t in the reference; their bounds fit unsigned.)
+template <typename T>
+struct MaxPointCountDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("seed", "srand seed", "1", "0", "2147483647", &P::Comp<unsigned>),
+                PDoc("maxCount", "maximum number of points", "1000", "0", "2147483647", &P::Comp<unsigned>)};
+    }
+    const size_t maxCount;
+    const size_t seed;
+    explicit MaxPointCountDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("MaxPointCountDataPointsFilter", doc(), p),
+          maxCount(this->template get<unsigned>("maxCount")),
+          seed(this->template get<unsigned>("seed")) {}
+    bool usesRandState() const override { return true; }
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        const size_t N = (size_t)(cloud.n - 1);  // (an empty cloud wraps, as in the reference: nothing to drop)
+        if (cloud.n == 0 || maxCount > N) return;
+        cloud.materialize();
+        std::srand((unsigned)seed);
+        const int rows = cloud.rows, dd = cloud.descDim;
+        for (size_t j = 0; j < maxCount; ++j) {
+            size_t idx = j + (size_t)((N - j) * ((float)(std::rand() / (float)RAND_MAX)));
+            if (idx > N) idx = N;  // (float(N - j) rounds up beyond 2^24 points; the reference indexes past its matrix)
+            if (idx == j) continue;
+            std::copy(&cloud.features[idx * rows], &cloud.features[idx * rows] + rows, &cloud.features[j * rows]);
+            if (dd > 0)
+                std::copy(&cloud.descriptors[idx * dd], &cloud.descriptors[idx * dd] + dd, &cloud.descriptors[j * dd]);
+        }
+        cloud.n = (int64_t)maxCount;
+        cloud.features.resize(maxCount * rows);
+        cloud.descriptors.resize(maxCount * (size_t)dd);
+    }
+};
+
 template <typename T>
 struct SamplingSurfaceNormalDPF : PM<T>::DataPointsFilter {
     typedef Parametrizable P;
@@ -1544,6 +1768,19 @@ PointMatcher<T>::PointMatcher() {
                                   [](const Ps& p) { return std::make_shared<VoxelGridDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("SamplingSurfaceNormalDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<SamplingSurfaceNormalDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("ShadowDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<ShadowDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("MaxQuantileOnAxisDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<MaxQuantileOnAxisDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("RemoveNaNDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<RemoveNaNDPF<T>>(p); }, false);
+    DataPointsFilterRegistrar.reg("CutAtDescriptorThresholdDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<CutAtDescriptorThresholdDPF<T>>(p); },
+                                  true);
+    DataPointsFilterRegistrar.reg("MaxDensityDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<MaxDensityDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("MaxPointCountDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<MaxPointCountDPF<T>>(p); }, true);
     InspectorRegistrar.reg("NullInspector", [](const Ps& p) {
         return std::make_shared<NoOp<Inspector>>("NullInspector", Parametrizable::ParametersDoc(), p);
     }, false);

@@ -302,6 +302,11 @@ int ssn_run(const P4<T>* d_pts, int D, int64_t n, int knn, T max_box, bool want_
 template <typename T>
 int voxel_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, const double vsize[3], bool centroid,
               bool avg, T* d_of, T* d_od, int64_t* n_out, hipStream_t st, std::string& err);
+// The keep-filters (pmx_keep.hip; pred / index / flag / value: pmx_keep_filter
+// of include/pmx.h): device in / out, capacity n
+template <typename T>
+int keep_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int pred, int index, int flag,
+             double value, T* d_of, T* d_od, int64_t* n_out, hipStream_t st, std::string& err);
 // code-object preloads (one per translation unit, called by pmx_ctx_create)
 void preload_setup();
 void preload_ssn();
@@ -339,6 +344,10 @@ void launch_reading_normals(const T* raw, int D, const int32_t* order, int64_t n
 // nth_element, Matches.cpp:110-120) instead of the quantile rule
 // (size_t)((T)count * ratio): passed as the select's ratio
 constexpr double kRatioMedianIndex = 2.0;
+// a given 0-based rank r among the finite keys (MaxQuantileOnAxis, pmx_keep.hip):
+// passed as kRatioRankBase + r, exact below 2^52; the per-pass select
+// (launch_select_pick) only
+constexpr double kRatioRankBase = 4.0;
 enum RobustScaleMode { kRSNone = 0, kRSMad = 1, kRSStd = 2, kRSBergFirst = 3, kRSBergNext = 4, kRSKeep = 5 };
 // dev[i] = |d[i] - median| for finite d (median: st->limit), +inf otherwise
 template <typename T>

@@ -173,6 +173,9 @@ __device__ __forceinline__ void pick_phase(uint32_t* __restrict__ hist, SelectSt
                 s_err = -2;  // PMX_E_EMPTY_QUANTILE: ConvergenceError("no outlier to filter")
             } else if (!ratio_dev && ratio_host == kRatioMedianIndex) {
                 st->rank = count / 2;  // nth_element at size / 2 (Matches.cpp:110-120)
+            } else if (!ratio_dev && ratio_host >= kRatioRankBase) {
+                unsigned long long r = (unsigned long long)(ratio_host - kRatioRankBase);  // a given rank
+                st->rank = r < count ? r : count - 1;
             } else if (q < (T)0 || q > (T)1) {
                 s_err = -3;  // ConvergenceError("quantile must be between 0 and 1")
             } else if (q == (T)1) {
