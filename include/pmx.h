@@ -621,6 +621,57 @@ int pmx_keep_filter(int device, int dtype, const void* feat, int rows, int64_t n
                     int predicate, int index, int flag, double value, void* feat_out, void* desc_out,
                     int64_t* n_out);
 
+/* IncidenceAngleDataPointsFilter (DataPointsFilters/IncidenceAngle.cpp:67-73):
+ * angles[i] = acos(normalized(obs_i) . normal_i), in T: normalized() is a
+ * sequential squared sum, a square root and a divide and leaves a zero vector
+ * as it is (Eigen 3.3), the dot is a sequential sum, the normal is taken as it
+ * comes.  normals, obs: span x n point-major T (span = 2 or 3, else
+ * PMX_E_BAD_PARAM); angles_out: n values.  The device acos is within a few ulp
+ * of the host library's, not bit-equal.  n = 0 is a result.  Standalone like
+ * pmx_voxel_grid; pmx_last_error(NULL) on failure. */
+int pmx_incidence_angles(int device, int dtype, const void* normals, const void* obs, int span, int64_t n,
+                         void* angles_out);
+
+/* SphericalityDataPointsFilter (DataPointsFilters/Sphericality.cpp:128-176):
+ * per point the three eigenvalues sorted ascending (e0 <= e1 <= e2), then
+ *   NaN for all three outputs when e2 < numeric_limits<T>::min(), e1 < 0 or e0 < 0,
+ *   0 when e1 < numeric_limits<T>::min(),
+ *   else unstructureness = e0 / e2, structureness = (e1 / e2) * ((e1 - e0) /
+ *   sqrt(e0 * e0 + e1 * e1)), sphericality = unstructureness - structureness,
+ * evaluated in T in that order: bit-identical to the reference (NaN
+ * eigenvalues aside: their sort order is unspecified there).  eig_values:
+ * 3 x n point-major T; sph_out: n values, always written; unstruct_out /
+ * struct_out: n values each, written when flags asks (else may be NULL).
+ * Standalone like pmx_voxel_grid; pmx_last_error(NULL) on failure. */
+enum { PMX_SPH_UNSTRUCTURENESS = 1, PMX_SPH_STRUCTURENESS = 2 };
+int pmx_sphericality(int device, int dtype, const void* eig_values, int64_t n, unsigned flags, void* sph_out,
+                     void* unstruct_out, void* struct_out);
+
+/* RemoveSensorBiasDataPointsFilter (DataPointsFilters/RemoveSensorBias.cpp:
+ * 108-127; getCoefficients / diffDist / ratioCurvature :132-187; constants
+ * RemoveSensorBias.h:94-113).  A point is kept when its incidence angle inc =
+ * desc[inc_row] is not NaN, inc >= 0 and inc < angle_threshold — the caller
+ * passes T(degrees / 180. * M_PI), compared in T.  A kept point moves along its
+ * observation direction obs = desc[obs_row .. obs_row + D): p + T(correction) *
+ * normalized(obs), correction = k1 * diffDist + k2 * ratioCurvature of the
+ * depth |obs| (formed in T) and inc, in double except the tan / cos / sin of
+ * inc, which are T calls as in the reference.  sensor_type: 0 Sick LMS-1xx,
+ * 1 Velodyne HDL-32E.  The kept points come out in their input order with
+ * their descriptors unchanged and the homogeneous row copied (the compaction
+ * of pmx_keep_filter); the kept set is exact.  The correction cancels eight
+ * digits, so for a double cloud sin / cos / tan of inc, erf and the two powers
+ * are rounded once from double-double arithmetic (about 104 bits: correctly
+ * rounded barring exact values within about 2^-100 of a rounding tie; inc in
+ * [0, pi / 2], erf's argument up to 3, i.e. depths to some 60 m; the device
+ * library's function beyond); a float cloud takes tanf / cosf / sinf.
+ * feat_out / desc_out hold n points.  n = 0 and a kept count of 0 are
+ * results.  PMX_E_BAD_PARAM for rows other than 3 or 4, inc_row or obs_row
+ * (+ D rows) outside desc, a sensor_type outside {0, 1}.  Standalone like
+ * pmx_voxel_grid; pmx_last_error(NULL) on failure. */
+int pmx_remove_sensor_bias(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc,
+                           int desc_dim, int inc_row, int obs_row, int sensor_type, double angle_threshold,
+                           void* feat_out, void* desc_out, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ missing, the calls raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -172,6 +173,7 @@ EXPORTS = [
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter",
+    "pmx_incidence_angles", "pmx_sphericality", "pmx_remove_sensor_bias",
 ]
 
 
@@ -248,6 +250,12 @@ def lib():
                                      C.POINTER(C.c_int64)]
         l.pmx_keep_filter.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        l.pmx_incidence_angles.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        l.pmx_sphericality.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
+        l.pmx_remove_sensor_bias.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_int64)]
         l.pmx_sampling_surface_normals.argtypes = ([C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint]
                                                    + [C.c_void_p] * 6 + [C.POINTER(C.c_int64)] * 2)
@@ -381,6 +389,94 @@ def keep_filter(points, descriptors, predicate, index=0, flag=0, value=0.0, devi
     rc = l.pmx_keep_filter(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n,
                            _ptr(desc) if dd else None, dd, int(predicate), int(index), int(flag), float(value),
                            _ptr(of), _ptr(od) if dd else None, C.byref(no))
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    return of[:no.value], od[:no.value]
+
+
+def _float_array(a, dtype=None):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float32)
+    return a
+
+
+def incidence_angles(normals, observation_directions, device=0):
+    """IncidenceAngleDataPointsFilter (IncidenceAngle.cpp:67-73) on the GPU
+    (pmx_incidence_angles, pmx_sensor.hip): acos(normalized(obs) . normal) per
+    point, in the arrays' type.  normals, observation_directions: (n, span),
+    span 2 or 3.  Returns (n,)."""
+    nrm = _float_array(normals)
+    obs = _float_array(observation_directions, nrm.dtype)
+    if nrm.ndim != 2 or obs.shape != nrm.shape:
+        raise InvalidParameter("incidence_angles: normals and observation directions must be (n, span) alike")
+    n, span = nrm.shape
+    out = np.empty(n, nrm.dtype)
+    l = lib()
+    rc = l.pmx_incidence_angles(int(device), PMX_F64 if nrm.dtype == np.float64 else PMX_F32, _ptr(nrm), _ptr(obs),
+                                span, n, _ptr(out))
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    return out
+
+
+SPH_UNSTRUCTURENESS, SPH_STRUCTURENESS = 1, 2  # PMX_SPH_*
+
+
+def sphericality(eig_values, keep_unstructureness=False, keep_structureness=False, device=0):
+    """SphericalityDataPointsFilter (Sphericality.cpp:128-176) on the GPU
+    (pmx_sphericality, pmx_sensor.hip).  eig_values: (n, 3), in any order.
+    Returns a dict of (n,) arrays: sphericality, and unstructureness /
+    structureness when asked."""
+    ev = _float_array(eig_values)
+    if ev.ndim != 2 or ev.shape[1] != 3:
+        raise InvalidParameter("sphericality: eig_values must be (n, 3)")
+    n, dt = ev.shape[0], ev.dtype
+    out = {"sphericality": np.empty(n, dt)}
+    if keep_unstructureness:
+        out["unstructureness"] = np.empty(n, dt)
+    if keep_structureness:
+        out["structureness"] = np.empty(n, dt)
+    flags = (SPH_UNSTRUCTURENESS if keep_unstructureness else 0) | (SPH_STRUCTURENESS if keep_structureness else 0)
+    l = lib()
+    rc = l.pmx_sphericality(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(ev), n, flags,
+                            _ptr(out["sphericality"]), _ptr(out.get("unstructureness")),
+                            _ptr(out.get("structureness")))
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    return out
+
+
+def angle_threshold(degrees, dtype):
+    """RemoveSensorBias's constructor (RemoveSensorBias.cpp:52): T(T(degrees) / 180. * M_PI)."""
+    T = np.dtype(dtype).type
+    return T(float(T(degrees)) / 180. * math.pi)
+
+
+def remove_sensor_bias(points, descriptors, inc_row, obs_row, sensor_type=0, angle_threshold_deg=88.0, device=0):
+    """RemoveSensorBiasDataPointsFilter (RemoveSensorBias.cpp:108-187) on the GPU
+    (pmx_remove_sensor_bias, pmx_sensor.hip).  points (n, rows) with the
+    homogeneous row last; descriptors (n, desc_dim) holding the incidence
+    angle in column inc_row and the observation direction in columns obs_row ..
+    obs_row + D; sensor_type 0 (LMS-1xx) or 1 (HDL-32E).  Returns (features,
+    descriptors) of the kept points, corrected, in their input order."""
+    pts = _float_array(points)
+    dt = pts.dtype
+    if pts.ndim != 2:
+        raise InvalidParameter("remove_sensor_bias: points must be (n, rows)")
+    n, rows = pts.shape
+    desc = None if descriptors is None else np.ascontiguousarray(descriptors, dtype=dt)
+    if desc is not None and (desc.ndim != 2 or desc.shape[0] != n):
+        raise InvalidParameter("remove_sensor_bias: descriptors must be (n, desc_dim) for the n points")
+    dd = 0 if desc is None else desc.shape[1]
+    of = np.empty((n, rows), dt)
+    od = np.empty((n, dd), dt)
+    no = C.c_int64(0)
+    l = lib()
+    rc = l.pmx_remove_sensor_bias(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n,
+                                  _ptr(desc) if dd else None, dd, int(inc_row), int(obs_row), int(sensor_type),
+                                  float(angle_threshold(angle_threshold_deg, dt)), _ptr(of), _ptr(od) if dd else None,
+                                  C.byref(no))
     if rc != PMX_OK:
         raise_for(rc, l.pmx_last_error(None).decode())
     return of[:no.value], od[:no.value]

@@ -1493,6 +1493,129 @@ struct CutAtDescriptorThresholdDPF : PM<T>::DataPointsFilter {
     }
 };
 
+// IncidenceAngleDataPointsFilter (DataPointsFilters/IncidenceAngle.cpp:50-74;
+// no parameter, IncidenceAngle.h:57-59): the descriptor "incidenceAngles" =
+// acos(normalized(observationDirection) . normal) on the device
+// (pmx_incidence_angles, pmx_sensor.hip).
+template <typename T>
+struct IncidenceAngleDPF : PM<T>::DataPointsFilter {
+    explicit IncidenceAngleDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("IncidenceAngleDataPointsFilter", Parametrizable::ParametersDoc(), p) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        if (!cloud.descriptorExists("normals"))
+            throw InvalidField("IncidenceAngleDataPointsFilter: Error, cannot find normals in descriptors.");
+        if (!cloud.descriptorExists("observationDirections"))
+            throw InvalidField(
+                "IncidenceAngleDataPointsFilter: Error, cannot find observation directions in descriptors.");
+        int span = 0, ospan = 0;
+        const std::vector<T> nrm = cloud.descriptor("normals", &span);
+        const std::vector<T> obs = cloud.descriptor("observationDirections", &ospan);
+        if (span != ospan)  // (an assertion in the reference)
+            throw InvalidField("IncidenceAngleDataPointsFilter: normals and observationDirections differ in rows");
+        std::vector<T> angles((size_t)cloud.n);
+        const int rc = pmx_incidence_angles(this->device, dtype_of<T>(), nrm.data(), obs.data(), span, cloud.n,
+                                            angles.data());
+        if (rc == PMX_E_BAD_PARAM) throw InvalidParameter(pmx_last_error(nullptr));
+        if (rc) throw std::runtime_error(pmx_last_error(nullptr));
+        cloud.setDescriptor("incidenceAngles", 1, angles.data());
+    }
+};
+
+// RemoveSensorBiasDataPointsFilter (DataPointsFilters/RemoveSensorBias.cpp:
+// 47-129, parameters RemoveSensorBias.h:67-73): the points whose incidence
+// angle is a number in [0, angleThreshold) move along their observation
+// direction by the sensor's bias model, the others are dropped
+// (pmx_remove_sensor_bias, pmx_sensor.hip).  The constructor takes the
+// threshold to radians in T.
+template <typename T>
+struct RemoveSensorBiasDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("sensorType", "Type of the sensor used. Choices: 0=Sick LMS-1xx, 1=Velodyne HDL-32E", "0", "0",
+                     "1", &P::Comp<int>),
+                PDoc("angleThreshold", "Threshold at which angle the correction is not applied, in degrees", "88.",
+                     "0.", "90.", &P::Comp<T>)};
+    }
+    const int sensorType;
+    const T angleThreshold;
+    explicit RemoveSensorBiasDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("RemoveSensorBiasDataPointsFilter", doc(), p),
+          sensorType(this->template get<int>("sensorType")),
+          angleThreshold((T)(this->template get<T>("angleThreshold") / 180. * M_PI)) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        int inc = 0, ispan = 0, obs = 0, ospan = 0;
+        if (!descriptor_rows(cloud, "incidenceAngles", inc, ispan))
+            throw InvalidField("RemoveSensorBiasDataPointsFilter: Error, cannot find incidence angles in descriptors.");
+        if (!descriptor_rows(cloud, "observationDirections", obs, ospan))
+            throw InvalidField(
+                "RemoveSensorBiasDataPointsFilter: Error, cannot find observationDirections in descriptors.");
+        if (sensorType != 0 && sensorType != 1)
+            throw InvalidParameter("RemoveSensorBiasDataPointsFilter: Error, cannot remove bias for sensorType id " +
+                                   std::to_string(sensorType) + " .");
+        if (ospan != cloud.rows - 1)  // (an Eigen size assertion in the reference's +=)
+            throw InvalidField("RemoveSensorBiasDataPointsFilter: observationDirections and points differ in rows");
+        cloud.materialize();
+        const int64_t n = cloud.n;
+        std::vector<T> feat((size_t)(n * cloud.rows)), desc((size_t)(n * cloud.descDim));
+        int64_t nout = 0;
+        const int rc = pmx_remove_sensor_bias(this->device, dtype_of<T>(), cloud.features.data(), cloud.rows, n,
+                                              cloud.descriptors.data(), cloud.descDim, inc, obs, sensorType,
+                                              (double)angleThreshold, feat.data(), desc.data(), &nout);
+        if (rc == PMX_E_BAD_PARAM) throw InvalidParameter(pmx_last_error(nullptr));
+        if (rc) throw std::runtime_error(pmx_last_error(nullptr));
+        cloud.n = nout;
+        feat.resize((size_t)(nout * cloud.rows));
+        cloud.features.swap(feat);
+        desc.resize((size_t)(nout * cloud.descDim));
+        cloud.descriptors.swap(desc);
+    }
+};
+
+// SphericalityDataPointsFilter (DataPointsFilters/Sphericality.cpp:49-177,
+// parameters Sphericality.h:72-78): the descriptor "sphericality", and
+// "unstructureness" / "structureness" when kept, from the three "eigValues"
+// (pmx_sphericality, pmx_sensor.hip).  keepStructureness is read as a T and
+// tested for non-zero, as in the reference.
+template <typename T>
+struct SphericalityDPF : PM<T>::DataPointsFilter {
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("keepUnstructureness",
+                     "whether the value of the unstructureness should be added to the pointcloud", "0"),
+                PDoc("keepStructureness", "whether the value of the structureness should be added to the pointcloud",
+                     "0")};
+    }
+    const int keepUnstructureness;
+    const T keepStructureness;
+    explicit SphericalityDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("SphericalityDataPointsFilter", doc(), p),
+          keepUnstructureness(this->template get<int>("keepUnstructureness")),
+          keepStructureness(this->template get<T>("keepStructureness")) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        if (!cloud.descriptorExists("eigValues"))
+            throw InvalidField("SphericalityDataPointsFilter: Error, no eigValues found in descriptors.");
+        int sum = 0;
+        for (auto& l : cloud.descriptorLabels) sum += l.span;
+        if (sum != cloud.descDim)  // (the reference's message names SurfaceNormal: Sphericality.cpp:94)
+            throw InvalidField(
+                "SurfaceNormalDataPointsFilter: Error, descriptor labels do not match descriptor data");
+        int span = 0;
+        const std::vector<T> eig = cloud.descriptor("eigValues", &span);
+        if (span != 3)
+            throw InvalidField("SphericalityDataPointsFilter: Error, the number of eigValues is not 3.");
+        const bool un = keepUnstructureness != 0, st = keepStructureness != (T)0;
+        const size_t n = (size_t)cloud.n;
+        std::vector<T> sph(n), uv(un ? n : 0), sv(st ? n : 0);
+        const int rc = pmx_sphericality(this->device, dtype_of<T>(), eig.data(), cloud.n,
+                                        (un ? PMX_SPH_UNSTRUCTURENESS : 0u) | (st ? PMX_SPH_STRUCTURENESS : 0u),
+                                        sph.data(), un ? uv.data() : nullptr, st ? sv.data() : nullptr);
+        if (rc == PMX_E_BAD_PARAM) throw InvalidParameter(pmx_last_error(nullptr));
+        if (rc) throw std::runtime_error(pmx_last_error(nullptr));
+        cloud.setDescriptor("sphericality", 1, sph.data());
+        if (un) cloud.setDescriptor("unstructureness", 1, uv.data());
+        if (st) cloud.setDescriptor("structureness", 1, sv.data());
+    }
+};
+
 // MaxDensityDataPointsFilter (DataPointsFilters/MaxDensity.cpp:44-105,
 // parameter MaxDensity.h:57-62): a point denser than maxDensity is kept when
 // (float)rand() / RAND_MAX < maxDensity / density, one draw per such point in
@@ -1777,6 +1900,12 @@ PointMatcher<T>::PointMatcher() {
     DataPointsFilterRegistrar.reg("CutAtDescriptorThresholdDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<CutAtDescriptorThresholdDPF<T>>(p); },
                                   true);
+    DataPointsFilterRegistrar.reg("IncidenceAngleDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<IncidenceAngleDPF<T>>(p); }, false);
+    DataPointsFilterRegistrar.reg("RemoveSensorBiasDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<RemoveSensorBiasDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("SphericalityDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<SphericalityDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("MaxDensityDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<MaxDensityDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("MaxPointCountDataPointsFilter",

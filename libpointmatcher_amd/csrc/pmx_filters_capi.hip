@@ -1,5 +1,6 @@
 // pmx_filters_capi.hip — the stand-alone data filters of include/pmx.h:
-// SurfaceNormal, SamplingSurfaceNormal, VoxelGrid and the keep-filters on the
+// SurfaceNormal, SamplingSurfaceNormal, VoxelGrid, the keep-filters and the
+// sensor-bias family (IncidenceAngle, Sphericality, RemoveSensorBias) on the
 // device, each on a temporary context or stream (the self-match of the normals
 // uses the grid match).
 #include "pmx_ctx.h"
@@ -216,6 +217,140 @@ int keep_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int
     return PMX_OK;
 }
 
+// A stream and one device allocation for a stand-alone elementwise filter
+struct FilterDevice {
+    hipStream_t st = nullptr;
+    char* buf = nullptr;
+    ~FilterDevice() {
+        if (buf) (void)hipFree(buf);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    int open(int device, size_t bytes, const char* who) {
+        if (hipSetDevice(device) != hipSuccess) {
+            g_err = std::string(who) + ": no HIP device";
+            return PMX_E_HIP;
+        }
+        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
+            hipMalloc(&buf, bytes) != hipSuccess) {
+            g_err = std::string(who) + ": device allocation failed";
+            return PMX_E_HIP;
+        }
+        return PMX_OK;
+    }
+};
+static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// IncidenceAngle, Sphericality (pmx_sensor.hip): upload, one kernel, download
+template <typename T>
+int incidence_impl(int device, const T* nrm, const T* obs, int span, int64_t n, T* out) {
+    const char* who = "IncidenceAngleDataPointsFilter";
+    if (span != 2 && span != 3) {
+        g_err = std::string(who) + ": normals and observationDirections must have 2 or 3 rows";
+        return PMX_E_BAD_PARAM;
+    }
+    if (n <= 0) return PMX_OK;
+    if (n > (int64_t)0x7fffffff) {
+        g_err = std::string(who) + ": more than 2^31 points";
+        return PMX_E_BAD_PARAM;
+    }
+    const size_t vb = sizeof(T) * (size_t)span * n, va = pad256(vb), ob = sizeof(T) * (size_t)n;
+    FilterDevice dev;
+    int rc = dev.open(device, 2 * va + ob, who);
+    if (rc) return rc;
+    T* d_n = (T*)dev.buf;
+    T* d_o = (T*)(dev.buf + va);
+    T* d_a = (T*)(dev.buf + 2 * va);
+    bool ok = hipMemcpyAsync(d_n, nrm, vb, hipMemcpyHostToDevice, dev.st) == hipSuccess &&
+              hipMemcpyAsync(d_o, obs, vb, hipMemcpyHostToDevice, dev.st) == hipSuccess;
+    if (ok) launch_incidence_angles<T>(d_n, d_o, span, n, d_a, dev.st);
+    ok = ok && hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(out, d_a, ob, hipMemcpyDeviceToHost, dev.st) == hipSuccess &&
+         hipStreamSynchronize(dev.st) == hipSuccess;
+    if (!ok) {
+        g_err = std::string(who) + ": HIP failure";
+        return PMX_E_HIP;
+    }
+    return PMX_OK;
+}
+
+template <typename T>
+int sphericality_impl(int device, const T* eig, int64_t n, T* o_sph, T* o_un, T* o_st) {
+    const char* who = "SphericalityDataPointsFilter";
+    if (n <= 0) return PMX_OK;
+    if (n > (int64_t)0x7fffffff) {
+        g_err = std::string(who) + ": more than 2^31 points";
+        return PMX_E_BAD_PARAM;
+    }
+    const size_t eb = sizeof(T) * 3 * (size_t)n, ea = pad256(eb), ob = sizeof(T) * (size_t)n, oa = pad256(ob);
+    FilterDevice dev;
+    int rc = dev.open(device, ea + 3 * oa, who);
+    if (rc) return rc;
+    T* d_e = (T*)dev.buf;
+    T* d_s = (T*)(dev.buf + ea);
+    T* d_u = o_un ? (T*)(dev.buf + ea + oa) : nullptr;
+    T* d_t = o_st ? (T*)(dev.buf + ea + 2 * oa) : nullptr;
+    bool ok = hipMemcpyAsync(d_e, eig, eb, hipMemcpyHostToDevice, dev.st) == hipSuccess;
+    if (ok) launch_sphericality<T>(d_e, n, d_s, d_u, d_t, dev.st);
+    ok = ok && hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(o_sph, d_s, ob, hipMemcpyDeviceToHost, dev.st) == hipSuccess &&
+         (!o_un || hipMemcpyAsync(o_un, d_u, ob, hipMemcpyDeviceToHost, dev.st) == hipSuccess) &&
+         (!o_st || hipMemcpyAsync(o_st, d_t, ob, hipMemcpyDeviceToHost, dev.st) == hipSuccess) &&
+         hipStreamSynchronize(dev.st) == hipSuccess;
+    if (!ok) {
+        g_err = std::string(who) + ": HIP failure";
+        return PMX_E_HIP;
+    }
+    return PMX_OK;
+}
+
+// RemoveSensorBias (pmx_sensor.hip): upload, correction + compaction, download
+// of the kept columns
+template <typename T>
+int sensor_bias_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int desc_dim, int inc_row,
+                     int obs_row, int sensor_type, double angle_threshold, T* feat_out, T* desc_out, int64_t* n_out) {
+    const char* who = "RemoveSensorBiasDataPointsFilter";
+    *n_out = 0;
+    std::string err;
+    int64_t m = 0;
+    // before the device is touched, and for an empty cloud too
+    int rc = sensor_bias_check(rows, n, desc_dim, inc_row, obs_row, sensor_type, err);
+    if (rc) g_err = err;
+    if (rc || n <= 0) return rc;
+    const size_t fb = sizeof(T) * (size_t)rows * n, db = sizeof(T) * (size_t)desc_dim * n;
+    const size_t fa = pad256(fb), da = pad256(db);
+    FilterDevice dev;
+    if ((rc = dev.open(device, 3 * fa + 2 * da, who))) return rc;
+    T* d_f = (T*)dev.buf;
+    T* d_cf = (T*)(dev.buf + fa);
+    T* d_of = (T*)(dev.buf + 2 * fa);
+    T* d_d = (T*)(dev.buf + 3 * fa);
+    T* d_od = (T*)(dev.buf + 3 * fa + da);
+    if (hipMemcpyAsync(d_f, feat, fb, hipMemcpyHostToDevice, dev.st) != hipSuccess ||
+        (db && hipMemcpyAsync(d_d, desc, db, hipMemcpyHostToDevice, dev.st) != hipSuccess)) {
+        g_err = std::string(who) + ": HIP failure";
+        return PMX_E_HIP;
+    }
+    rc = sensor_bias_run<T>(d_f, rows, n, db ? d_d : nullptr, desc_dim, inc_row, obs_row, sensor_type, angle_threshold,
+                            d_cf, d_of, d_od, &m, dev.st, err);
+    if (rc) {
+        g_err = err.empty() ? std::string(who) + ": HIP failure" : err;
+        return rc;
+    }
+    if (m > 0 && (hipMemcpyAsync(feat_out, d_of, sizeof(T) * (size_t)rows * m, hipMemcpyDeviceToHost, dev.st) !=
+                      hipSuccess ||
+                  hipMemcpyAsync(desc_out, d_od, sizeof(T) * (size_t)desc_dim * m, hipMemcpyDeviceToHost, dev.st) !=
+                      hipSuccess)) {
+        g_err = std::string(who) + ": HIP failure";
+        return PMX_E_HIP;
+    }
+    if (hipStreamSynchronize(dev.st) != hipSuccess) {
+        g_err = std::string(who) + ": HIP failure";
+        return PMX_E_HIP;
+    }
+    *n_out = m;
+    return PMX_OK;
+}
+
 template <typename T>
 int ssn_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int desc_dim, int knn, int method,
              double ratio_d, double max_box_d, unsigned flags, T* feat_out, T* desc_out, T* o_nrm, T* o_dens,
@@ -392,6 +527,57 @@ int pmx_keep_filter(int device, int dtype, const void* feat, int rows, int64_t n
     if (dtype == PMX_F64)
         return keep_impl<double>(device, (const double*)feat, rows, n, (const double*)desc, desc_dim, predicate, index,
                                  flag, value, (double*)feat_out, (double*)desc_out, n_out);
+    g_err = "dtype must be PMX_F32 or PMX_F64";
+    return PMX_E_BAD_PARAM;
+}
+
+int pmx_incidence_angles(int device, int dtype, const void* normals, const void* obs, int span, int64_t n,
+                         void* angles_out) {
+    if (n > 0 && (!normals || !obs || !angles_out)) {
+        g_err = "null argument";
+        return PMX_E_BAD_PARAM;
+    }
+    if (dtype == PMX_F32)
+        return incidence_impl<float>(device, (const float*)normals, (const float*)obs, span, n, (float*)angles_out);
+    if (dtype == PMX_F64)
+        return incidence_impl<double>(device, (const double*)normals, (const double*)obs, span, n,
+                                      (double*)angles_out);
+    g_err = "dtype must be PMX_F32 or PMX_F64";
+    return PMX_E_BAD_PARAM;
+}
+
+int pmx_sphericality(int device, int dtype, const void* eig_values, int64_t n, unsigned flags, void* sph_out,
+                     void* unstruct_out, void* struct_out) {
+    const bool un = (flags & PMX_SPH_UNSTRUCTURENESS) != 0, st = (flags & PMX_SPH_STRUCTURENESS) != 0;
+    if (n > 0 && (!eig_values || !sph_out || (un && !unstruct_out) || (st && !struct_out))) {
+        g_err = "null argument";
+        return PMX_E_BAD_PARAM;
+    }
+    if (dtype == PMX_F32)
+        return sphericality_impl<float>(device, (const float*)eig_values, n, (float*)sph_out,
+                                        un ? (float*)unstruct_out : nullptr, st ? (float*)struct_out : nullptr);
+    if (dtype == PMX_F64)
+        return sphericality_impl<double>(device, (const double*)eig_values, n, (double*)sph_out,
+                                         un ? (double*)unstruct_out : nullptr, st ? (double*)struct_out : nullptr);
+    g_err = "dtype must be PMX_F32 or PMX_F64";
+    return PMX_E_BAD_PARAM;
+}
+
+int pmx_remove_sensor_bias(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc,
+                           int desc_dim, int inc_row, int obs_row, int sensor_type, double angle_threshold,
+                           void* feat_out, void* desc_out, int64_t* n_out) {
+    if (!n_out || (n > 0 && (!feat || !feat_out || (desc_dim > 0 && (!desc || !desc_out))))) {
+        g_err = "null argument";
+        return PMX_E_BAD_PARAM;
+    }
+    if (dtype == PMX_F32)
+        return sensor_bias_impl<float>(device, (const float*)feat, rows, n, (const float*)desc, desc_dim, inc_row,
+                                       obs_row, sensor_type, angle_threshold, (float*)feat_out, (float*)desc_out,
+                                       n_out);
+    if (dtype == PMX_F64)
+        return sensor_bias_impl<double>(device, (const double*)feat, rows, n, (const double*)desc, desc_dim, inc_row,
+                                        obs_row, sensor_type, angle_threshold, (double*)feat_out, (double*)desc_out,
+                                        n_out);
     g_err = "dtype must be PMX_F32 or PMX_F64";
     return PMX_E_BAD_PARAM;
 }

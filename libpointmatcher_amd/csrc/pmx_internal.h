@@ -307,6 +307,59 @@ int voxel_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, 
 template <typename T>
 int keep_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int pred, int index, int flag,
              double value, T* d_of, T* d_od, int64_t* n_out, hipStream_t st, std::string& err);
+// The stable compaction under them (pmx_keep.hip), for any kernel that decides
+// one point per thread in blocks of kKeepBlock: the kernel ends in
+// keep_block_ballot, keep_compact scans the block counts and copies the kept
+// columns of d_f / d_desc to d_of / d_od (capacity n) in point order.
+constexpr int kKeepBlock = 256;  // points per block: one per thread, four waves
+constexpr int kKeepWaves = kKeepBlock / 64;
+struct KeepScratch {
+    unsigned long long* masks = nullptr;  // one ballot per wave
+    uint32_t* cnt = nullptr;              // kept points per block
+    uint32_t* off = nullptr;              // their exclusive scan, off[nb] = the kept count
+    int64_t nb = 0;
+    KeepScratch() = default;
+    KeepScratch(const KeepScratch&) = delete;
+    KeepScratch& operator=(const KeepScratch&) = delete;
+    ~KeepScratch() {
+        if (masks) (void)hipFree(masks);
+    }
+    int alloc(int64_t n);  // PMX_OK or PMX_E_HIP
+};
+// k: the calling thread's point is kept (false past n).  Every thread of the
+// block calls it; the wave's 64-bit ballot and the block's kept count are stored.
+__device__ __forceinline__ void keep_block_ballot(bool k, unsigned long long* __restrict__ masks,
+                                                  uint32_t* __restrict__ block_cnt) {
+    __shared__ uint32_t wc[kKeepWaves];
+    const unsigned long long m = __ballot(k);  // 64 lanes
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        masks[(int64_t)blockIdx.x * kKeepWaves + wave] = m;
+        wc[wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (int w = 0; w < kKeepWaves; ++w) c += wc[w];
+        block_cnt[blockIdx.x] = c;
+    }
+}
+template <typename T>
+int keep_compact(const T* d_f, int rows, const T* d_desc, int desc_dim, const KeepScratch& s, T* d_of,
+                 T* d_od, int64_t* n_out, hipStream_t st);
+// IncidenceAngle, Sphericality and RemoveSensorBias (pmx_sensor.hip); device
+// pointers, point-major.  sensor_bias_run: d_cf is scratch of rows x n for the
+// corrected features; outputs of capacity n.  sensor_bias_check: its parameter
+// checks (they hold for an empty cloud too), PMX_OK or PMX_E_BAD_PARAM with err set
+int sensor_bias_check(int rows, int64_t n, int desc_dim, int inc_row, int obs_row, int sensor_type, std::string& err);
+template <typename T>
+void launch_incidence_angles(const T* nrm, const T* obs, int span, int64_t n, T* angles, hipStream_t st);
+template <typename T>
+void launch_sphericality(const T* eig, int64_t n, T* sph, T* unstruct, T* structure, hipStream_t st);
+template <typename T>
+int sensor_bias_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int inc_row, int obs_row,
+                    int sensor_type, double angle_threshold, T* d_cf, T* d_of, T* d_od, int64_t* n_out,
+                    hipStream_t st, std::string& err);
 // code-object preloads (one per translation unit, called by pmx_ctx_create)
 void preload_setup();
 void preload_ssn();

@@ -48,8 +48,7 @@
 
 namespace pmx {
 
-constexpr int kKeepBlock = 256;  // points per block: one per thread, four waves
-constexpr int kKeepWaves = kKeepBlock / 64;
+// (kKeepBlock points per block, one per thread, four waves: pmx_internal.h)
 
 template <typename T>
 struct KeepArgs {
@@ -129,22 +128,10 @@ __global__ __launch_bounds__(kKeepBlock) void keep_flag_kernel(const T* __restri
                                                                int64_t n, KeepArgs<T> a,
                                                                unsigned long long* __restrict__ masks,
                                                                uint32_t* __restrict__ block_cnt) {
-    __shared__ uint32_t wc[kKeepWaves];
     const int64_t i = (int64_t)blockIdx.x * kKeepBlock + threadIdx.x;
     bool k = false;
     if (i < n) k = keep_pred<T>(a, f + i * a.rows, d + i * a.desc_dim);
-    const unsigned long long m = __ballot(k);  // 64 lanes
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        masks[(int64_t)blockIdx.x * kKeepWaves + wave] = m;
-        wc[wave] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t c = 0;
-        for (int w = 0; w < kKeepWaves; ++w) c += wc[w];
-        block_cnt[blockIdx.x] = c;
-    }
+    keep_block_ballot(k, masks, block_cnt);
 }
 
 // off[b] = kept points of the blocks before b; off[nb] = the kept count
@@ -379,33 +366,53 @@ int keep_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, i
             return rc;
         }
     }
-    const int64_t nb = (n + kKeepBlock - 1) / kKeepBlock;
+    KeepScratch sc;
+    if (sc.alloc(n) != PMX_OK) {
+        err = "keep filter: device allocation failed";
+        return PMX_E_HIP;
+    }
+    hipLaunchKernelGGL(keep_flag_kernel<T>, dim3((unsigned)sc.nb), dim3(kKeepBlock), 0, st, d_f, d_desc, n, a,
+                       sc.masks, sc.cnt);
+    if (keep_compact<T>(d_f, rows, d_desc, desc_dim, sc, d_of, d_od, n_out, st) != PMX_OK) {
+        err = "keep filter: HIP failure";
+        return PMX_E_HIP;
+    }
+    return PMX_OK;
+}
+
+int KeepScratch::alloc(int64_t n) {
+    nb = (n + kKeepBlock - 1) / kKeepBlock;
     char* buf = nullptr;
     const size_t mb = sizeof(unsigned long long) * (size_t)nb * kKeepWaves;
     const size_t cb = (sizeof(uint32_t) * (size_t)nb + 255) & ~(size_t)255;
     const size_t ob = sizeof(uint32_t) * (size_t)(nb + 1);
-    if (hipMalloc(&buf, mb + cb + ob) != hipSuccess) {
-        err = "keep filter: device allocation failed";
-        return PMX_E_HIP;
-    }
-    std::unique_ptr<void, void (*)(void*)> free_buf(buf, [](void* p) { (void)hipFree(p); });
-    unsigned long long* masks = (unsigned long long*)buf;
-    uint32_t* cnt = (uint32_t*)(buf + mb);
-    uint32_t* off = (uint32_t*)(buf + mb + cb);
-    hipLaunchKernelGGL(keep_flag_kernel<T>, dim3((unsigned)nb), dim3(kKeepBlock), 0, st, d_f, d_desc, n, a, masks, cnt);
-    hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(256), 0, st, cnt, nb, off);
-    hipLaunchKernelGGL(keep_scatter_kernel<T>, dim3((unsigned)nb), dim3(kKeepBlock), 0, st, d_f, d_desc, rows,
-                       desc_dim, masks, off, d_of, d_od);
+    if (hipMalloc(&buf, mb + cb + ob) != hipSuccess) return PMX_E_HIP;
+    masks = (unsigned long long*)buf;
+    cnt = (uint32_t*)(buf + mb);
+    off = (uint32_t*)(buf + mb + cb);
+    return PMX_OK;
+}
+
+// the scan and the scatter over the ballots and block counts a flag kernel left in s
+template <typename T>
+int keep_compact(const T* d_f, int rows, const T* d_desc, int desc_dim, const KeepScratch& s, T* d_of,
+                 T* d_od, int64_t* n_out, hipStream_t st) {
+    hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(256), 0, st, s.cnt, s.nb, s.off);
+    hipLaunchKernelGGL(keep_scatter_kernel<T>, dim3((unsigned)s.nb), dim3(kKeepBlock), 0, st, d_f, d_desc, rows,
+                       desc_dim, s.masks, s.off, d_of, d_od);
     uint32_t kept = 0;
     if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(&kept, off + nb, sizeof(kept), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        err = "keep filter: HIP failure";
+        hipMemcpyAsync(&kept, s.off + s.nb, sizeof(kept), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
         return PMX_E_HIP;
-    }
     *n_out = (int64_t)kept;
     return PMX_OK;
 }
+
+template int keep_compact<float>(const float*, int, const float*, int, const KeepScratch&, float*, float*,
+                                 int64_t*, hipStream_t);
+template int keep_compact<double>(const double*, int, const double*, int, const KeepScratch&, double*, double*,
+                                  int64_t*, hipStream_t);
 
 template int keep_run<float>(const float*, int, int64_t, const float*, int, int, int, int, double, float*, float*,
                              int64_t*, hipStream_t, std::string&);
