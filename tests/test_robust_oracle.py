@@ -18,79 +18,7 @@ import numpy as np
 import pytest
 
 from helpers import hom, rel_displacement
-
-FCTS = ["cauchy", "welsch", "sc", "gm", "tukey", "huber", "L1", "student"]
-BERG = {"cauchy": 4.3040, "tukey": 7.0589, "huber": 2.0138}
-
-
-class NpRobust:
-    """numpy restatement of the reference object (constructor + robustFiltering)."""
-
-    def __init__(self, dtype, fct="cauchy", tuning=1.0, scale="mad", nb=0, approx=np.inf):
-        T = np.dtype(dtype).type
-        self.T, self.fct, self.scale_est, self.nb = T, fct, scale, nb
-        self.k = T(tuning)
-        self.target = T(0)
-        if scale == "berg":
-            self.target = T(tuning)
-            if fct in BERG:
-                self.k = T(BERG[fct])
-        self.sqa = T(np.inf) if np.isinf(approx) else T(T(approx) ** 2)
-        self.it, self.scale = 1, T(0)
-
-    def weights(self, d):
-        T = self.T
-        rec = self.it <= self.nb or self.nb == 0
-        fin = d[np.isfinite(d)]
-        if self.scale_est == "mad" and rec:
-            med = np.sort(fin)[len(fin) // 2]
-            dev = np.abs(fin - med).astype(T)
-            self.scale = T(np.sqrt(np.sort(dev)[len(dev) // 2]))
-        elif self.scale_est == "std" and rec:
-            s = np.sum(d.astype(np.float64))
-            mean = T(s / d.size)
-            c = (d - mean).astype(T)
-            var = T(T(np.sum((c * c).astype(np.float64))) / T(d.size - 1))
-            self.scale = T(np.sqrt(T(np.sqrt(var))))
-        elif self.scale_est == "berg" and rec:
-            if self.it == 1:
-                q = np.partition(fin, int(T(len(fin)) * T(0.5)))[int(T(len(fin)) * T(0.5))]
-                self.scale = T(1.9 * float(T(np.sqrt(q))))
-            else:
-                self.scale = T(T(0.85) * (self.scale - self.target) + self.target)
-        elif self.scale_est == "none":
-            self.scale = T(1)
-        self.it += 1
-        with np.errstate(all="ignore"):
-            e2 = (d / (self.scale * self.scale)).astype(T)
-            k, k2 = self.k, T(self.k * self.k)
-            one = T(1)
-            f = self.fct
-            if f == "cauchy":
-                w = one / (one + e2 / k2)
-            elif f == "welsch":
-                w = np.exp(-e2 / k2)
-            elif f == "sc":
-                s = (k + e2).astype(T)
-                w = np.where(e2 >= k, T(4.0 * float(k2)) * (one / (s * s)), one)
-            elif f == "gm":
-                s = (k + e2).astype(T)
-                w = k2 * (one / (s * s))
-            elif f == "tukey":
-                a = (one - e2 / k2).astype(T)
-                w = np.where(e2 >= k2, T(0), a * a)
-            elif f == "huber":
-                w = np.where(e2 >= k2, k * (one / np.sqrt(e2)), one)
-            elif f == "L1":
-                w = one / np.sqrt(e2)
-            else:
-                dd = T(3)
-                w = np.power(one + e2 / k, -(k + dd) / T(2)) * (k + dd) * (one / (k + e2))
-            w = w.astype(T)
-            w = np.where(w <= T(1e-50), T(1e-50), w).astype(T)
-            if not np.isinf(self.sqa):
-                w = np.where(e2 >= self.sqa, T(0), w).astype(T)
-        return w
+from robust_cases import FCTS, NpRobust  # (the numpy restatement, shared with the edge cases)
 
 
 def _dists(dtype, n=2000, k=3, seed=0, inf_frac=0.05):
