@@ -621,6 +621,49 @@ int pmx_keep_filter(int device, int dtype, const void* feat, int rows, int64_t n
                     int predicate, int index, int flag, double value, void* feat_out, void* desc_out,
                     int64_t* n_out);
 
+/* OctreeGridDataPointsFilter (DataPointsFilters/OctreeGrid.cpp:48-366, the tree
+ * utils/octree.hpp:229-385): one point per non-empty leaf of an octree (rows =
+ * 4) or quadtree (rows = 3).  Root box octree.hpp:238-251 in T; a node is a
+ * leaf when double(radius) * 2 <= max_size_by_node or it holds <=
+ * max_point_by_node points (:312), else each point goes to child
+ * sum_i (p_i > center_i) << i (:181-189) of radius radius * 0.5 and centre
+ * center +- 0.5 * radius, rounded in T (:335-341).  Leaves come in the
+ * reference's visit order (:373-385: depth first, children 0 .. 2^dim - 1,
+ * empty ones skipped), their members by rising input index; the leaves are the
+ * literal recursion's whatever its depth (duplicates with max_size_by_node 0
+ * end only when the radius underflows to 0).  sampling_method:
+ *   0 first     the first member of each leaf (OctreeGrid.cpp:48-71)
+ *   1 random    member size_t((n - 1) * float(rand() / float(RAND_MAX))), the
+ *               product in float; srand(1), one rand() per leaf in visit
+ *               order, srand(1) again (:85-137): the call draws from the
+ *               process's rand() state on the calling thread and leaves it as
+ *               srand(1) does
+ *   2 centroid  feature rows but the homogeneous one, and every descriptor row:
+ *               the sequential sum in T over the members in order, divided by
+ *               T(n); the homogeneous row of the first member (:147-210)
+ *   3 medoid    the first member strictly nearest the leaf's mean (sequential
+ *               sums from 0; dist = sqrt((dx*dx + dy*dy) + dz*dz) in T)
+ *               (:219-282)
+ * Methods 0 and 1 are bit-identical to the reference, output column order
+ * included: the reference moves pick k to column k by swapCols and a lookup
+ * table (:55-67) that is one level deep and goes stale, so its kept columns
+ * are not always the picks; that sequence is replayed on column numbers on the
+ * host and whole columns are gathered.  Methods 2 and 3 DIVERGE from the
+ * reference where it misbehaves: the reference reads and accumulates columns
+ * through the same stale table, so its output depends on wrongly addressed
+ * columns step by step; here column k is the centroid or medoid of leaf k
+ * computed from the input cloud's own columns.  The two agree whenever no
+ * lookup is stale, e.g. for a cloud already in visit order.
+ * desc: desc_dim x n (may be NULL with desc_dim 0); feat_out / desc_out hold n
+ * points.  n = 0 returns 0 points.  Non-finite coordinates are outside the
+ * contract (a non-finite bounding box is PMX_E_BAD_PARAM); n < 2^31.
+ * PMX_E_BAD_PARAM for rows other than 3 or 4, a sampling_method outside 0..3,
+ * max_point_by_node < 1 or max_size_by_node < 0.  Deterministic (no atomics).
+ * Standalone like pmx_voxel_grid; pmx_last_error(NULL) on failure. */
+int pmx_octree_grid(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc, int desc_dim,
+                    int64_t max_point_by_node, double max_size_by_node, int sampling_method, void* feat_out,
+                    void* desc_out, int64_t* n_out);
+
 /* IncidenceAngleDataPointsFilter (DataPointsFilters/IncidenceAngle.cpp:67-73):
  * angles[i] = acos(normalized(obs_i) . normal_i), in T: normalized() is a
  * sequential squared sum, a square root and a divide and leaves a zero vector

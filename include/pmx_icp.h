@@ -62,6 +62,8 @@ const char* pmx_icp_last_error(const pmx_icp* icp);
  * "- name (default: v) - doc[ - min: a][ - max: b]".  PMX_ICP_INVALID_ELEMENT for
  * an unknown name, PMX_ICP_INVALID_PARAMETER when cap is too small. */
 int pmx_icp_outlier_filter_doc(int dtype, const char* name, char* out, int cap);
+/* The same dump for a registered data points filter. */
+int pmx_icp_data_points_filter_doc(int dtype, const char* name, char* out, int cap);
 int pmx_icp_set_default(pmx_icp* icp);
 int pmx_icp_load_yaml(pmx_icp* icp, const char* yaml_text);
 /* multi-GPU: call before the first compute; uid from pmx_comm_unique_id */

@@ -172,7 +172,7 @@ EXPORTS = [
     "pmx_p2plane_system", "pmx_p2plane_system_forced", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
-    "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter",
+    "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter", "pmx_octree_grid",
     "pmx_incidence_angles", "pmx_sphericality", "pmx_remove_sensor_bias",
 ]
 
@@ -250,6 +250,8 @@ def lib():
                                      C.POINTER(C.c_int64)]
         l.pmx_keep_filter.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        l.pmx_octree_grid.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64,
+                                      C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         l.pmx_incidence_angles.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
         l.pmx_sphericality.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
@@ -389,6 +391,39 @@ def keep_filter(points, descriptors, predicate, index=0, flag=0, value=0.0, devi
     rc = l.pmx_keep_filter(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n,
                            _ptr(desc) if dd else None, dd, int(predicate), int(index), int(flag), float(value),
                            _ptr(of), _ptr(od) if dd else None, C.byref(no))
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    return of[:no.value], od[:no.value]
+
+
+OCTREE_FIRST, OCTREE_RANDOM, OCTREE_CENTROID, OCTREE_MEDOID = range(4)  # samplingMethod
+
+
+def octree_grid(points, descriptors=None, max_point_by_node=1, max_size_by_node=0.0, sampling_method=OCTREE_FIRST,
+                device=0):
+    """OctreeGridDataPointsFilter (DataPointsFilters/OctreeGrid.cpp:48-366,
+    utils/octree.hpp:229-385) on the GPU (pmx_octree_grid, pmx_octree.hip): one
+    point per non-empty leaf of the octree (rows 4) or quadtree (rows 3), in
+    the reference's visit order.  sampling_method 0 first, 1 random (draws
+    from the process's rand() state between two srand(1)), 2 centroid, 3
+    medoid; 0 and 1 are bit-identical to the reference, 2 and 3 are computed
+    per leaf from the input cloud (include/pmx.h).  points (n, rows) with the
+    homogeneous row last; descriptors (n, desc_dim) or None.  Returns
+    (features, descriptors) of the kept points."""
+    pts = np.ascontiguousarray(points)
+    if pts.dtype not in (np.float32, np.float64):
+        pts = pts.astype(np.float32)
+    dt = pts.dtype
+    n, rows = pts.shape
+    dd = 0 if descriptors is None else descriptors.shape[1]
+    desc = None if descriptors is None else np.ascontiguousarray(descriptors, dtype=dt)
+    of = np.empty((n, rows), dt)
+    od = np.empty((n, dd), dt)
+    no = C.c_int64(0)
+    l = lib()
+    rc = l.pmx_octree_grid(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n,
+                           _ptr(desc) if dd else None, dd, int(max_point_by_node), float(max_size_by_node),
+                           int(sampling_method), _ptr(of), _ptr(od) if dd else None, C.byref(no))
     if rc != PMX_OK:
         raise_for(rc, l.pmx_last_error(None).decode())
     return of[:no.value], od[:no.value]

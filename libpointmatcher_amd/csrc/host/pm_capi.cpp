@@ -575,22 +575,40 @@ int pmx_cloud_label(const pmx_cloud* c, int which, int i, char* name, int cap, i
 }
 
 // Parametrizable's documentation dump (Parametrizable.cpp:51-74) of a
-// registered outlier filter: "- name (default: v) - doc[ - min: a][ - max: b]" per line
+// registered module: "- name (default: v) - doc[ - min: a][ - max: b]" per line
+extern "C++" template <typename Module>
+int dump_parameters_doc(const Module& f, char* out, int cap) {
+    std::string s;
+    for (const auto& p : f->parametersDoc) {
+        s += "- " + p.name + " (default: " + p.defaultValue + ") - " + p.doc;
+        if (!p.minValue.empty()) s += " - min: " + p.minValue;
+        if (!p.maxValue.empty()) s += " - max: " + p.maxValue;
+        s += "\n";
+    }
+    if ((int)s.size() >= cap) return PMX_ICP_INVALID_PARAMETER;
+    std::snprintf(out, (size_t)cap, "%s", s.c_str());
+    return PMX_ICP_OK;
+}
+
 int pmx_icp_outlier_filter_doc(int dtype, const char* name, char* out, int cap) {
     if (!name || !out || cap < 1 || (dtype != 0 && dtype != 1)) return PMX_ICP_INVALID_PARAMETER;
     auto dump = [&](const auto& pm) -> int {
         try {
-            const auto f = pm.OutlierFilterRegistrar.create(name);
-            std::string s;
-            for (const auto& p : f->parametersDoc) {
-                s += "- " + p.name + " (default: " + p.defaultValue + ") - " + p.doc;
-                if (!p.minValue.empty()) s += " - min: " + p.minValue;
-                if (!p.maxValue.empty()) s += " - max: " + p.maxValue;
-                s += "\n";
-            }
-            if ((int)s.size() >= cap) return PMX_ICP_INVALID_PARAMETER;
-            std::snprintf(out, (size_t)cap, "%s", s.c_str());
-            return PMX_ICP_OK;
+            return dump_parameters_doc(pm.OutlierFilterRegistrar.create(name), out, cap);
+        } catch (const InvalidElement&) {
+            return PMX_ICP_INVALID_ELEMENT;
+        } catch (const std::exception&) {
+            return PMX_ICP_RUNTIME_ERROR;
+        }
+    };
+    return dtype == 1 ? dump(pm::PointMatcher<double>::get()) : dump(pm::PointMatcher<float>::get());
+}
+
+int pmx_icp_data_points_filter_doc(int dtype, const char* name, char* out, int cap) {
+    if (!name || !out || cap < 1 || (dtype != 0 && dtype != 1)) return PMX_ICP_INVALID_PARAMETER;
+    auto dump = [&](const auto& pm) -> int {
+        try {
+            return dump_parameters_doc(pm.DataPointsFilterRegistrar.create(name), out, cap);
         } catch (const InvalidElement&) {
             return PMX_ICP_INVALID_ELEMENT;
         } catch (const std::exception&) {

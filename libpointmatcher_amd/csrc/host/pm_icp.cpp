@@ -1363,6 +1363,58 @@ struct VoxelGridDPF : PM<T>::DataPointsFilter {
     }
 };
 
+// OctreeGridDataPointsFilter (DataPointsFilters/OctreeGrid.h:80-83,
+// OctreeGrid.cpp:284-366) on the device (pmx_octree_grid, pmx_octree.hip): one
+// point per non-empty leaf, in the reference's visit order.  First and random
+// sampling are bit-identical to the reference, its swapCols / mapidx column
+// order included; centroid and medoid are computed per leaf from the input
+// cloud (the reference addresses columns through a table that goes stale: see
+// include/pmx.h).  buildParallel is accepted and changes nothing.  The random
+// sampler brackets its draws with srand(1) as the reference does, so every
+// call resets the process's rand() state.
+template <typename T>
+struct OctreeGridDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("buildParallel", "If 1 (true), use threads to build the octree.", "1", "0", "1", &P::Comp<bool>),
+                PDoc("maxPointByNode", "Number of point under which the octree stop dividing.", "1", "1", "4294967295",
+                     &P::Comp<std::size_t>),
+                PDoc("maxSizeByNode", "Size of the bounding box under which the octree stop dividing.", "0", "0", "+inf",
+                     &P::Comp<T>),
+                PDoc("samplingMethod", "Method to sample the Octree: First Point (0), Random (1), Centroid (2) (more "
+                                       "accurate but costly), Medoid (3) (more accurate but costly)",
+                     "0", "0", "3", &P::Comp<int>)};
+    }
+    const bool buildParallel;
+    const std::size_t maxPointByNode;
+    const T maxSizeByNode;
+    const int samplingMethod;
+    explicit OctreeGridDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("OctreeGridDataPointsFilter", doc(), p),
+          buildParallel(this->template get<bool>("buildParallel")),
+          maxPointByNode(this->template get<std::size_t>("maxPointByNode")),
+          maxSizeByNode(this->template get<T>("maxSizeByNode")),
+          samplingMethod(this->template get<int>("samplingMethod")) {}
+    bool usesRandState() const override { return samplingMethod == 1; }
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        cloud.materialize();
+        const int64_t n = cloud.n;
+        std::vector<T> feat((size_t)(n * cloud.rows)), desc((size_t)(n * cloud.descDim));
+        int64_t nout = 0;
+        const int rc = pmx_octree_grid(this->device, dtype_of<T>(), cloud.features.data(), cloud.rows, n,
+                                       cloud.descDim ? cloud.descriptors.data() : nullptr, cloud.descDim,
+                                       (int64_t)maxPointByNode, (double)maxSizeByNode, samplingMethod, feat.data(),
+                                       cloud.descDim ? desc.data() : nullptr, &nout);
+        if (rc == PMX_E_BAD_PARAM) throw InvalidParameter(pmx_last_error(nullptr));
+        if (rc) throw std::runtime_error(std::string("OctreeGridDataPointsFilter: ") + pmx_last_error(nullptr));
+        cloud.n = nout;
+        feat.resize((size_t)(nout * cloud.rows));
+        cloud.features.swap(feat);
+        desc.resize((size_t)(nout * cloud.descDim));
+        cloud.descriptors.swap(desc);
+    }
+};
+
 // The keep-filters on the device (pmx_keep_filter, pmx_keep.hip): a per-point
 // predicate and a stable compaction of features and descriptors.
 template <typename T>
@@ -1889,6 +1941,8 @@ PointMatcher<T>::PointMatcher() {
                                   [](const Ps& p) { return std::make_shared<DistanceLimitDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("VoxelGridDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<VoxelGridDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("OctreeGridDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<OctreeGridDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("SamplingSurfaceNormalDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<SamplingSurfaceNormalDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("ShadowDataPointsFilter",

@@ -66,6 +66,15 @@ unsigned lexical_cast<unsigned>(const std::string& s) {
     return parse_int<unsigned>(t);
 }
 template <>
+std::size_t lexical_cast<std::size_t>(const std::string& s) {  // (OctreeGrid's maxPointByNode)
+    const std::string t = trim(s);
+    if (!t.empty() && t[0] == '-') throw InvalidParameter("bad lexical cast: \"" + t + "\"");
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(t.c_str(), &end, 10);
+    if (t.empty() || end != t.c_str() + t.size()) throw InvalidParameter("bad lexical cast: \"" + t + "\"");
+    return (std::size_t)v;
+}
+template <>
 bool lexical_cast<bool>(const std::string& s) {
     const std::string t = trim(s);
     if (t == "1" || t == "true") return true;

@@ -1,5 +1,5 @@
 // pmx_filters_capi.hip — the stand-alone data filters of include/pmx.h:
-// SurfaceNormal, SamplingSurfaceNormal, VoxelGrid, the keep-filters and the
+// SurfaceNormal, SamplingSurfaceNormal, VoxelGrid, OctreeGrid, the keep-filters and the
 // sensor-bias family (IncidenceAngle, Sphericality, RemoveSensorBias) on the
 // device, each on a temporary context or stream (the self-match of the normals
 // uses the grid match).
@@ -205,6 +205,58 @@ int keep_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int
                                err);
     if (rc) {
         g_err = err.empty() ? std::string("keep filter: HIP failure") : err;
+        return rc;
+    }
+    if (m > 0 && hipMemcpyAsync(feat_out, d_of, sizeof(T) * (size_t)rows * m, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return PMX_E_HIP;
+    if (m > 0 && db && desc_out &&
+        hipMemcpyAsync(desc_out, d_od, sizeof(T) * (size_t)desc_dim * m, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return PMX_E_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return PMX_E_HIP;
+    *n_out = m;
+    return PMX_OK;
+}
+
+// OctreeGridDataPointsFilter (pmx_octree.hip): upload, the tree walk and the
+// sampler, download of the kept columns
+template <typename T>
+int octree_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int desc_dim, int64_t max_pts,
+                double max_size, int method, T* feat_out, T* desc_out, int64_t* n_out) {
+    *n_out = 0;
+    std::string err;
+    int64_t m = 0;
+    if (n <= 0) {  // (the parameter checks of octree_run still apply to an empty cloud)
+        const int rc = octree_run<T>(nullptr, rows, 0, nullptr, desc_dim, max_pts, max_size, method, nullptr, nullptr,
+                                     &m, nullptr, err);
+        if (rc) g_err = err;
+        return rc;
+    }
+    if (hipSetDevice(device) != hipSuccess) {
+        g_err = "OctreeGridDataPointsFilter: no HIP device";
+        return PMX_E_HIP;
+    }
+    hipStream_t st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return PMX_E_HIP;
+    std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> free_st(
+        st, [](hipStream_t s) { (void)hipStreamDestroy(s); });
+    const size_t fb = sizeof(T) * (size_t)rows * n, db = sizeof(T) * (size_t)desc_dim * n;
+    const size_t fa = (fb + 255) & ~(size_t)255, da = (db + 255) & ~(size_t)255;
+    char* buf = nullptr;
+    if (hipMalloc(&buf, 2 * (fa + da)) != hipSuccess) {
+        g_err = "OctreeGridDataPointsFilter: device allocation failed";
+        return PMX_E_HIP;
+    }
+    std::unique_ptr<void, void (*)(void*)> free_buf(buf, [](void* p) { (void)hipFree(p); });
+    T* d_f = (T*)buf;
+    T* d_d = (T*)(buf + fa);
+    T* d_of = (T*)(buf + fa + da);
+    T* d_od = (T*)(buf + 2 * fa + da);
+    if (hipMemcpyAsync(d_f, feat, fb, hipMemcpyHostToDevice, st) != hipSuccess) return PMX_E_HIP;
+    if (db && hipMemcpyAsync(d_d, desc, db, hipMemcpyHostToDevice, st) != hipSuccess) return PMX_E_HIP;
+    const int rc = octree_run<T>(d_f, rows, n, db ? d_d : nullptr, desc_dim, max_pts, max_size, method, d_of, d_od, &m,
+                                 st, err);
+    if (rc) {
+        g_err = err.empty() ? std::string("OctreeGridDataPointsFilter: HIP failure") : err;
         return rc;
     }
     if (m > 0 && hipMemcpyAsync(feat_out, d_of, sizeof(T) * (size_t)rows * m, hipMemcpyDeviceToHost, st) != hipSuccess)
@@ -527,6 +579,25 @@ int pmx_keep_filter(int device, int dtype, const void* feat, int rows, int64_t n
     if (dtype == PMX_F64)
         return keep_impl<double>(device, (const double*)feat, rows, n, (const double*)desc, desc_dim, predicate, index,
                                  flag, value, (double*)feat_out, (double*)desc_out, n_out);
+    g_err = "dtype must be PMX_F32 or PMX_F64";
+    return PMX_E_BAD_PARAM;
+}
+
+int pmx_octree_grid(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc, int desc_dim,
+                    int64_t max_point_by_node, double max_size_by_node, int sampling_method, void* feat_out,
+                    void* desc_out, int64_t* n_out) {
+    if ((!feat && n > 0) || (desc_dim > 0 && !desc && n > 0) || !n_out || (!feat_out && n > 0) ||
+        (desc_dim > 0 && !desc_out && n > 0)) {
+        g_err = "null argument";
+        return PMX_E_BAD_PARAM;
+    }
+    if (dtype == PMX_F32)
+        return octree_impl<float>(device, (const float*)feat, rows, n, (const float*)desc, desc_dim, max_point_by_node,
+                                  max_size_by_node, sampling_method, (float*)feat_out, (float*)desc_out, n_out);
+    if (dtype == PMX_F64)
+        return octree_impl<double>(device, (const double*)feat, rows, n, (const double*)desc, desc_dim,
+                                   max_point_by_node, max_size_by_node, sampling_method, (double*)feat_out,
+                                   (double*)desc_out, n_out);
     g_err = "dtype must be PMX_F32 or PMX_F64";
     return PMX_E_BAD_PARAM;
 }

@@ -347,6 +347,12 @@ __device__ __forceinline__ void keep_block_ballot(bool k, unsigned long long* __
 template <typename T>
 int keep_compact(const T* d_f, int rows, const T* d_desc, int desc_dim, const KeepScratch& s, T* d_of,
                  T* d_od, int64_t* n_out, hipStream_t st);
+// OctreeGridDataPointsFilter (pmx_octree.hip; the parameters: pmx_octree_grid of
+// include/pmx.h): device in / out, capacity n.  The random sampler draws from
+// the process's rand() state on the calling thread.
+template <typename T>
+int octree_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int64_t max_pts, double max_size,
+               int method, T* d_of, T* d_od, int64_t* n_out, hipStream_t st, std::string& err);
 // IncidenceAngle, Sphericality and RemoveSensorBias (pmx_sensor.hip); device
 // pointers, point-major.  sensor_bias_run: d_cf is scratch of rows x n for the
 // corrected features; outputs of capacity n.  sensor_bias_check: its parameter

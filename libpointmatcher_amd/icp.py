@@ -75,6 +75,7 @@ def lib():
                                              C.c_void_p]
         l.pmx_icp_keep_trace.argtypes = [C.c_void_p, C.c_int]
         l.pmx_icp_outlier_filter_doc.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int]
+        l.pmx_icp_data_points_filter_doc.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int]
         l.pmx_icp_add_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_int64]
         l.pmx_cloud_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         l.pmx_cloud_destroy.argtypes = [C.c_void_p]
@@ -120,6 +121,17 @@ def outlier_filter_doc(name, dtype=np.float32):
     rc = lib().pmx_icp_outlier_filter_doc(1 if np.dtype(dtype) == np.float64 else 0, name.encode(), buf, len(buf))
     if rc:
         raise _ERR.get(rc, RuntimeError)(f"no documentation for outlier filter {name}")
+    return buf.value.decode()
+
+
+def data_points_filter_doc(name, dtype=np.float32):
+    """The parameter documentation of a registered data points filter, in the
+    form of outlier_filter_doc."""
+    buf = C.create_string_buffer(8192)
+    rc = lib().pmx_icp_data_points_filter_doc(1 if np.dtype(dtype) == np.float64 else 0, name.encode(), buf,
+                                              len(buf))
+    if rc:
+        raise _ERR.get(rc, RuntimeError)(f"no documentation for data points filter {name}")
     return buf.value.decode()
 
 
