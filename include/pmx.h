@@ -664,6 +664,53 @@ int pmx_octree_grid(int device, int dtype, const void* feat, int rows, int64_t n
                     int64_t max_point_by_node, double max_size_by_node, int sampling_method, void* feat_out,
                     void* desc_out, int64_t* n_out);
 
+/* NormalSpaceDataPointsFilter (DataPointsFilters/NormalSpace.cpp:47-181,
+ * parameters NormalSpace.h:63-70): normal-space sampling of a 3-D cloud with
+ * normals (desc rows normals_row .. normals_row + 2).  In the reference's call
+ * order: rows = 3 (a 2-D cloud, :73-77), nb_sample >= n (:81) and n = 0 copy
+ * the input to the outputs and draw nothing.  Otherwise the point indices are
+ * shuffled by std::random_shuffle as libstdc++ runs it — for i = 1 .. n-1, j =
+ * rand() % (i + 1), swap when i != j — i.e. n - 1 draws from the process's
+ * rand() state on the calling thread, which is left where they leave it (seed
+ * does not touch it; :100-102).  In that order each point goes to bucket
+ * size_t(floor(theta / eps) * cols + floor(phi / eps)) with theta = acos(nz)
+ * and phi = T(fmod(double(atan2(ny, nx)) + 2 pi, 2 pi)), theta == T(pi) and
+ * phi == 2 T(pi) wrapped to 0 (so nz = -1 lands in row 0), the divisions and
+ * floors in T, the product and sum in double; cols = ceil(2.0 * M_PI / eps),
+ * rows = ceil(M_PI / eps), nbBucket = size_t(cols * rows), eps = T(epsilon)
+ * (:53, :114-116, :169-181).  Empty buckets are removed; nb_sample times a
+ * bucket is drawn from std::mt19937(seed) with
+ * std::uniform_int_distribution<size_t>(0, buckets left - 1), its last member
+ * is taken and popped, and the bucket is erased once empty (:129-145).  The
+ * picks move to the front by the swapCols / mapidx sequence of
+ * pmx_octree_grid's methods 0 and 1, stale lookups included (:149-165).
+ * The certificate: the device evaluates theta, phi and both quotients in fp64
+ * and keeps its bucket only where both quotients are farther from an integer,
+ * theta from pi and phi from 0 and 2 pi, than the host function's error in T,
+ * the device function's in fp64 and the rounding of the T division can
+ * separate the two evaluations (pmx_nss.hip, kNss*; the device acos / atan2 are
+ * within a few ulp of the host library's, not bit-equal).  Every other point
+ * is evaluated on the host with the literal T expression; *n_recheck (may be
+ * NULL) is their count.  The grouping is a stable sort, no atomics, so the
+ * result is deterministic and bit-identical to the reference, output column
+ * order included, on a host whose acos / atan2 / fmod agree with the reference
+ * build's.
+ * Inputs the reference leaves undefined are refused with PMX_E_BAD_PARAM and a
+ * message naming the first offending point: a normal with a NaN or |nz| > 1
+ * (its asserts :108-111), and a bucket index >= nbBucket (the T division can
+ * round theta / eps up to rows; a release build writes out of range).  Also
+ * PMX_E_BAD_PARAM: rows other than 3 or 4, nb_sample < 1, epsilon outside
+ * [0.04908738521, 3.14159265359] compared in T, n >= 2^31, and — when the
+ * sampling runs — normals_row < 0 or normals_row + 3 > desc_dim.  An error
+ * return draws nothing, and the GPU runtime's own use of rand() / srand() is
+ * kept off the caller's state (initstate / setstate around every HIP call).
+ * desc: desc_dim x n point-major; feat_out / desc_out
+ * hold n points.  Standalone like pmx_voxel_grid;
+ * pmx_last_error(NULL) on failure. */
+int pmx_normal_space(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc, int desc_dim,
+                     int normals_row, int64_t nb_sample, uint64_t seed, double epsilon, void* feat_out,
+                     void* desc_out, int64_t* n_out, int64_t* n_recheck);
+
 /* IncidenceAngleDataPointsFilter (DataPointsFilters/IncidenceAngle.cpp:67-73):
  * angles[i] = acos(normalized(obs_i) . normal_i), in T: normalized() is a
  * sequential squared sum, a square root and a divide and leaves a zero vector

@@ -15,9 +15,16 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
-__all__ = ["build", "HERE", "ROOT"]
+__all__ = ["build", "normal_space", "HERE", "ROOT"]
 
 
 def build(jobs: int = 8) -> None:
     """Compile libpmx.so (HIP, gfx950) and libpmx_icp.so in-tree."""
     subprocess.check_call(["make", "-s", "-C", HERE, f"-j{jobs}", "all"])
+
+
+def normal_space(*args, **kwargs):
+    """NormalSpaceDataPointsFilter on the GPU: _capi.normal_space (imported on
+    first use, so that importing the package needs no built library)."""
+    from ._capi import normal_space as impl
+    return impl(*args, **kwargs)

@@ -173,6 +173,7 @@ EXPORTS = [
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter", "pmx_octree_grid",
+    "pmx_normal_space",
     "pmx_incidence_angles", "pmx_sphericality", "pmx_remove_sensor_bias",
 ]
 
@@ -252,6 +253,9 @@ def lib():
                                       C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         l.pmx_octree_grid.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64,
                                       C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        l.pmx_normal_space.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int64, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         l.pmx_incidence_angles.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
         l.pmx_sphericality.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
@@ -427,6 +431,36 @@ def octree_grid(points, descriptors=None, max_point_by_node=1, max_size_by_node=
     if rc != PMX_OK:
         raise_for(rc, l.pmx_last_error(None).decode())
     return of[:no.value], od[:no.value]
+
+
+def normal_space(points, descriptors, normals_row=0, nb_sample=5000, seed=1, epsilon=0.09817477042, device=0):
+    """NormalSpaceDataPointsFilter (DataPointsFilters/NormalSpace.cpp:47-181) on
+    the GPU (pmx_normal_space, pmx_nss.hip): nb_sample points drawn from the
+    buckets of the normals' directions, bit-identical to the reference, column
+    order included.  The shuffle draws n - 1 times from the process's rand()
+    state; seed feeds the mt19937 of the picks; epsilon is cast to the cloud's
+    type.  points (n, rows) with the homogeneous row last; descriptors
+    (n, desc_dim) holding the normals at columns normals_row .. normals_row + 2.
+    A 2-D cloud, nb_sample >= n and n = 0 return the cloud as it is.  Returns
+    (features, descriptors, n_recheck): n_recheck points were evaluated on the
+    host because the device could not certify their bucket (include/pmx.h)."""
+    pts = np.ascontiguousarray(points)
+    if pts.dtype not in (np.float32, np.float64):
+        pts = pts.astype(np.float32)
+    dt = pts.dtype
+    n, rows = pts.shape
+    dd = 0 if descriptors is None else descriptors.shape[1]
+    desc = None if descriptors is None else np.ascontiguousarray(descriptors, dtype=dt)
+    of = np.empty((n, rows), dt)
+    od = np.empty((n, dd), dt)
+    no, nr = C.c_int64(0), C.c_int64(0)
+    l = lib()
+    rc = l.pmx_normal_space(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n,
+                            _ptr(desc) if dd else None, dd, int(normals_row), int(nb_sample), int(seed),
+                            float(epsilon), _ptr(of), _ptr(od) if dd else None, C.byref(no), C.byref(nr))
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    return of[:no.value], od[:no.value], nr.value
 
 
 def _float_array(a, dtype=None):

@@ -1449,6 +1449,58 @@ bool descriptor_rows(const DataPoints<T>& cloud, const std::string& name, int& o
     return false;
 }
 
+// NormalSpaceDataPointsFilter (DataPointsFilters/NormalSpace.h:63-70,
+// NormalSpace.cpp:47-181) on the device (pmx_normal_space, pmx_nss.hip): nbSample
+// points drawn from the buckets of the normals' directions, bit-identical to
+// the reference, its column order included (include/pmx.h).  The early exits in
+// the reference's order: a 2-D cloud is left as it is with a message, then
+// nbSample >= n, then the missing normals.  The shuffle draws n - 1 times from
+// the process's rand() state; seed only feeds the mt19937 of the picks.
+template <typename T>
+struct NormalSpaceDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("nbSample", "Number of point to select.", "5000", "1", "4294967295", &P::Comp<std::size_t>),
+                PDoc("seed", "Seed for the random generator.", "1", "0", "4294967295", &P::Comp<std::size_t>),
+                PDoc("epsilon", "Step of discretization for the angle spaces", "0.09817477042", "0.04908738521",
+                     "3.14159265359", &P::Comp<T>)};
+    }
+    const std::size_t nbSample;
+    const std::size_t seed;
+    const T epsilon;
+    explicit NormalSpaceDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("NormalSpaceDataPointsFilter", doc(), p),
+          nbSample(this->template get<std::size_t>("nbSample")),
+          seed(this->template get<std::size_t>("seed")),
+          epsilon(this->template get<T>("epsilon")) {}
+    bool usesRandState() const override { return true; }
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        if (cloud.rows < 4) {  // NormalSpace.cpp:73-77
+            std::cerr << "ERROR: NormalSpaceDataPointsFilter does not support 2D point cloud yet (does nothing)"
+                      << std::endl;
+            return;
+        }
+        if (nbSample >= (std::size_t)cloud.n) return;  // :81
+        int off = 0, span = 0;
+        if (!descriptor_rows(cloud, "normals", off, span))  // :85-86 (the reference's text)
+            throw InvalidField("OrientNormalsDataPointsFilter: Error, cannot find normals in descriptors.");
+        cloud.materialize();
+        const int64_t n = cloud.n;
+        std::vector<T> feat((size_t)(n * cloud.rows)), desc((size_t)(n * cloud.descDim));
+        int64_t nout = 0;
+        const int rc = pmx_normal_space(this->device, dtype_of<T>(), cloud.features.data(), cloud.rows, n,
+                                        cloud.descriptors.data(), cloud.descDim, off, (int64_t)nbSample,
+                                        (uint64_t)seed, (double)epsilon, feat.data(), desc.data(), &nout, nullptr);
+        if (rc == PMX_E_BAD_PARAM) throw InvalidParameter(pmx_last_error(nullptr));
+        if (rc) throw std::runtime_error(std::string("NormalSpaceDataPointsFilter: ") + pmx_last_error(nullptr));
+        cloud.n = nout;
+        feat.resize((size_t)(nout * cloud.rows));
+        cloud.features.swap(feat);
+        desc.resize((size_t)(nout * cloud.descDim));
+        cloud.descriptors.swap(desc);
+    }
+};
+
 // ShadowDataPointsFilter (DataPointsFilters/Shadow.cpp:44-94, parameter
 // Shadow.h:60-65): keep |normalized(normal) . normalized(point)| > sin(eps);
 // the constructor takes the sine in T.
@@ -1943,6 +1995,8 @@ PointMatcher<T>::PointMatcher() {
                                   [](const Ps& p) { return std::make_shared<VoxelGridDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("OctreeGridDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<OctreeGridDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("NormalSpaceDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<NormalSpaceDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("SamplingSurfaceNormalDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<SamplingSurfaceNormalDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("ShadowDataPointsFilter",

@@ -353,6 +353,18 @@ int keep_compact(const T* d_f, int rows, const T* d_desc, int desc_dim, const Ke
 template <typename T>
 int octree_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int64_t max_pts, double max_size,
                int method, T* d_of, T* d_od, int64_t* n_out, hipStream_t st, std::string& err);
+// NormalSpaceDataPointsFilter (pmx_nss.hip; the parameters: pmx_normal_space of
+// include/pmx.h) past the reference's early exits (rows 4, 1 <= nb_sample < n <
+// 2^31, nrow + 3 <= desc_dim, eps in range).  h_desc: the host's descriptors
+// (the rechecked points are evaluated from them); the rest device in / out,
+// capacity nb_sample.  Draws n - 1 times from the process's rand() state on the
+// calling thread, after the keys are known (an error return draws nothing); rs
+// holds that state aside during every HIP call (common/pmx_nss.h).
+class NssRandState;
+template <typename T>
+int nss_run(const T* h_desc, const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int nrow,
+            int64_t nb_sample, uint64_t seed, T eps, T* d_of, T* d_od, int64_t* n_out, int64_t* n_recheck,
+            NssRandState& rs, hipStream_t st, std::string& err);
 // IncidenceAngle, Sphericality and RemoveSensorBias (pmx_sensor.hip); device
 // pointers, point-major.  sensor_bias_run: d_cf is scratch of rows x n for the
 // corrected features; outputs of capacity n.  sensor_bias_check: its parameter

@@ -58,6 +58,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common/pmx_octree_replay.h"
+#include "pmx_columns.h"
 #include "pmx_internal.h"
 #include "pmx_sort.h"
 
@@ -273,11 +274,6 @@ __global__ __launch_bounds__(256) void oct_leaf_of_point_kernel(const uint32_t* 
     if (pos < n) leaf[order[pos]] = hoff[pos] + head[pos] - 1u;
 }
 
-__global__ __launch_bounds__(256) void oct_iota_kernel(uint32_t* __restrict__ a, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = (uint32_t)i;
-}
-
 // first / random: the pick of leaf k (OctreeGrid.cpp:53, 104-109); fac null: the first member
 __global__ __launch_bounds__(256) void oct_pick_kernel(const uint32_t* __restrict__ order,
                                                        const uint32_t* __restrict__ segs, int64_t L, int64_t n,
@@ -293,17 +289,6 @@ __global__ __launch_bounds__(256) void oct_pick_kernel(const uint32_t* __restric
         if (id > last) id = last;  // (float(last) rounds up beyond 2^24 members; the reference reads past its vector)
     }
     pick[k] = (int32_t)order[a + (uint32_t)id];
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void oct_gather_kernel(const T* __restrict__ f, const T* __restrict__ d, int rows,
-                                                         int desc_dim, const int32_t* __restrict__ src, int64_t L,
-                                                         T* __restrict__ of, T* __restrict__ od) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= L) return;
-    const int64_t s = src[k];
-    for (int r = 0; r < rows; ++r) of[k * rows + r] = f[s * rows + r];
-    for (int r = 0; r < desc_dim; ++r) od[k * desc_dim + r] = d[s * desc_dim + r];
 }
 
 template <typename T>
@@ -521,7 +506,7 @@ int octree_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim,
         const uint32_t* aidx = first ? nullptr : idxA;
         const uint32_t* aseg = first ? nullptr : seg;
         const uint32_t* apos = first ? nullptr : posA;
-        if (first) hipLaunchKernelGGL(oct_iota_kernel, dim3(oct_blocks(m)), dim3(256), 0, st, idxA, m);
+        if (first) hipLaunchKernelGGL(iota_kernel<uint32_t>, dim3(oct_blocks(m)), dim3(256), 0, st, idxA, m);
         if (D == 3)
             launch_oct_key<T, 3>(d_f, rows, aidx, aseg, m, root, K, limit, state, keyA, stop, st);
         else
@@ -557,7 +542,7 @@ int octree_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim,
     }
 
     // ---- the leaves: the positions whose head flag is set ----
-    hipLaunchKernelGGL(oct_iota_kernel, dim3(oct_blocks(n)), dim3(256), 0, st, posA, n);
+    hipLaunchKernelGGL(iota_kernel<uint32_t>, dim3(oct_blocks(n)), dim3(256), 0, st, posA, n);
     size_t t = tb;
     if (hipcub::DeviceSelect::Flagged(temp, t, posA, head, segs, nsel, (int)n, st) != hipSuccess) return PMX_E_HIP;
     int64_t L = 0;
@@ -608,7 +593,7 @@ int octree_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim,
         int32_t* d_col = (int32_t*)idxB;
         if (hipMemcpyAsync(d_col, col.data(), sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, st) != hipSuccess)
             return PMX_E_HIP;
-        hipLaunchKernelGGL(oct_gather_kernel<T>, dim3(oct_blocks(L)), dim3(256), 0, st, d_f, d_desc, rows, desc_dim,
+        hipLaunchKernelGGL(gather_columns_kernel<T>, dim3(oct_blocks(L)), dim3(256), 0, st, d_f, d_desc, rows, desc_dim,
                            d_col, L, d_of, d_od);
     }
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PMX_E_HIP;
