@@ -711,6 +711,79 @@ int pmx_normal_space(int device, int dtype, const void* feat, int rows, int64_t 
                      int normals_row, int64_t nb_sample, uint64_t seed, double epsilon, void* feat_out,
                      void* desc_out, int64_t* n_out, int64_t* n_recheck);
 
+/* CovarianceSamplingDataPointsFilter (DataPointsFilters/CovarianceSampling.cpp:
+ * 74-250, parameters CovarianceSampling.h:70-76; Gelfand et al. 2003): stability
+ * sampling of a 3-D cloud with normals (desc rows normals_row .. normals_row +
+ * 2): the nb_sample points that best constrain the six degrees of freedom of
+ * the point-to-plane system.  In the reference's call order: rows != 4 is
+ * PMX_E_BAD_PARAM (:77 only asserts; a release build would read the
+ * homogeneous row as z); nb_sample >= n and n = 0 copy the input to the
+ * outputs (:81), before any look at the normals; then normals_row < 0 or
+ * normals_row + 3 > desc_dim is PMX_E_BAD_PARAM (:85).
+ * Everything below is in T (the cloud's type) unless said otherwise, every
+ * multiply and add rounded on its own, on the device and on the host alike;
+ * only +, -, x, / and sqrt occur, so the two agree bit for bit.
+ *   centre (:103-110)  each coordinate sum in fp64 over a fixed grid in a
+ *     fixed order, divided by n in fp64, rounded to T.  The reference sums
+ *     sequentially in T: the last bits of c may differ (divergence 1).
+ *   L (:113-133)  torque_norm 0: 1.  1: the mean of sqrt((dx dx + dy dy) +
+ *     dz dz), each term in T, the sum in fp64 (fixed order), divided by n,
+ *     rounded to T.  2: half the largest of the three extents max - min, the
+ *     reference's value exactly.
+ *   v_i (:142-148, :169-173)  inv = T(1.0 / double(L)); v_i = [inv * ((p_i - c)
+ *     x n_i) ; n_i], each cross-product component a * b - c * d.
+ *   cov (:152)  the 21 upper-triangle sums of v_r * v_c, each product in T,
+ *     accumulated in fp64 in a fixed order, then mirrored.
+ *   basis  The reference takes the eigenvectors of Eigen's non-symmetric
+ *     EigenSolver (:158-160), whose column order and signs are implementation-
+ *     defined.  With basis NULL the library defines them (divergence 2): cyclic
+ *     Jacobi on the symmetric cov in double on the host, eigenvalues ascending
+ *     (list 0 serves the least constrained direction), each vector's largest
+ *     component positive, rounded to T.  A supplied basis (36 doubles,
+ *     row-major 6 x 6, column k is X_k, e.g. Eigen's) is rounded to T and used
+ *     as given, in the caller's column order.
+ *   projections (:189, :224)  m_k(i) = ((((v0 x0 + v1 x1) + v2 x2) + v3 x3) + v4
+ *     x4) + v5 x5 with x = X_k; the reference's Eigen dot may add in another
+ *     order (divergence 3).
+ *   lists (:177-193)  list k holds the point indices by falling fabs(m_k), ties
+ *     by rising index (std::list::sort is stable): a stable device sort on the
+ *     inverted bit pattern of fabs(m).
+ *   picks (:195-229), on the host, literally: t[6] in T from 0; k the first
+ *     index of the smallest t; fronts of list k already sampled are dropped;
+ *     the front is picked; t[j] += m_j * m_j for all six j with the picked
+ *     point's signed projections.  Every entry read from a list is a distinct
+ *     point that ends up sampled, so no list is read past position nb_sample
+ *     and only that many entries of each list reach the host.
+ *   columns (:233-249)  the picks move to the front by the swapCols / mapidx
+ *     sequence of pmx_octree_grid's methods 0 and 1, stale lookups included.
+ * Given the centre, L and basis, the selection and the output column order are
+ * the reference's, bit for bit; report (may be NULL) returns those three as
+ * used — center and lnorm as doubles holding T values, eigvec the basis after
+ * rounding to T (row-major, column k is X_k) — with cov, eigval (the Jacobi
+ * eigenvalues of cov, ascending, whichever basis is used) and depth, the
+ * deepest 1-based list position read (<= nb_sample).  An early exit reports
+ * zeros.
+ * Also PMX_E_BAD_PARAM: nb_sample < 1; torque_norm outside 0..2; n >= 2^31; a
+ * non-finite coordinate or normal, with a message naming the first such point;
+ * L = 0 under torque_norm 1 or 2 (every point at the centroid); a supplied
+ * basis with an entry that is not finite in T.  Projections that overflow T
+ * are outside the contract.  The filter draws nothing from rand(); the GPU
+ * runtime's own use of it is kept off the caller's state (initstate / setstate
+ * around every HIP call, as pmx_normal_space).  No atomics: deterministic.
+ * desc: desc_dim x n point-major; feat_out / desc_out hold n points.
+ * Standalone like pmx_voxel_grid; pmx_last_error(NULL) on failure. */
+typedef struct pmx_covs_report {
+    double center[3];
+    double lnorm;
+    double cov[36];
+    double eigval[6];
+    double eigvec[36];
+    int64_t depth;
+} pmx_covs_report;
+int pmx_covariance_sampling(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc,
+                            int desc_dim, int normals_row, int64_t nb_sample, int torque_norm, const double* basis,
+                            void* feat_out, void* desc_out, int64_t* n_out, pmx_covs_report* report);
+
 /* IncidenceAngleDataPointsFilter (DataPointsFilters/IncidenceAngle.cpp:67-73):
  * angles[i] = acos(normalized(obs_i) . normal_i), in T: normalized() is a
  * sequential squared sum, a square root and a divide and leaves a zero vector

@@ -15,7 +15,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
-__all__ = ["build", "normal_space", "HERE", "ROOT"]
+__all__ = ["build", "normal_space", "covariance_sampling", "HERE", "ROOT"]
 
 
 def build(jobs: int = 8) -> None:
@@ -27,4 +27,12 @@ def normal_space(*args, **kwargs):
     """NormalSpaceDataPointsFilter on the GPU: _capi.normal_space (imported on
     first use, so that importing the package needs no built library)."""
     from ._capi import normal_space as impl
+    return impl(*args, **kwargs)
+
+
+def covariance_sampling(*args, **kwargs):
+    """CovarianceSamplingDataPointsFilter on the GPU: _capi.covariance_sampling
+    (imported on first use, so that importing the package needs no built
+    library)."""
+    from ._capi import covariance_sampling as impl
     return impl(*args, **kwargs)

@@ -173,7 +173,7 @@ EXPORTS = [
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter", "pmx_octree_grid",
-    "pmx_normal_space",
+    "pmx_normal_space", "pmx_covariance_sampling",
     "pmx_incidence_angles", "pmx_sphericality", "pmx_remove_sensor_bias",
 ]
 
@@ -256,6 +256,9 @@ def lib():
         l.pmx_normal_space.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                        C.c_int64, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        l.pmx_covariance_sampling.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
+                                              C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int64), C.POINTER(CovsReport)]
         l.pmx_incidence_angles.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
         l.pmx_sphericality.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_uint, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
@@ -461,6 +464,56 @@ def normal_space(points, descriptors, normals_row=0, nb_sample=5000, seed=1, eps
     if rc != PMX_OK:
         raise_for(rc, l.pmx_last_error(None).decode())
     return of[:no.value], od[:no.value], nr.value
+
+
+class CovsReport(C.Structure):
+    """pmx_covs_report of include/pmx.h."""
+    _fields_ = [("center", C.c_double * 3), ("lnorm", C.c_double), ("cov", C.c_double * 36),
+                ("eigval", C.c_double * 6), ("eigvec", C.c_double * 36), ("depth", C.c_int64)]
+
+
+def covariance_sampling(points, descriptors, normals_row=0, nb_sample=5000, torque_norm=1, basis=None, device=0):
+    """CovarianceSamplingDataPointsFilter (DataPointsFilters/CovarianceSampling.cpp:
+    74-250) on the GPU (pmx_covariance_sampling, pmx_covs.hip): the nb_sample
+    points that best constrain the six degrees of freedom of the point-to-plane
+    system.  torque_norm 0 L = 1, 1 L = the mean distance from the centroid,
+    2 L = half the largest extent.  basis: None for the library's own (Jacobi on
+    the symmetric covariance, eigenvalues ascending, largest component positive)
+    or a (6, 6) array whose column k is X_k, used as given after rounding to the
+    cloud's type.  points (n, 4) with the homogeneous row last; descriptors
+    (n, desc_dim) holding the normals at columns normals_row .. normals_row + 2.
+    nb_sample >= n and n = 0 return the cloud as it is.  Returns (features,
+    descriptors, report): report is a dict of center (3,), lnorm, cov (6, 6),
+    eigval (6,), eigvec (6, 6) — the centre, L and basis as used — and depth,
+    the deepest list position read (include/pmx.h).  eigval always holds the
+    library's own eigenvalues of cov, ascending: with a supplied basis it does
+    not correspond to the columns of eigvec."""
+    pts = np.ascontiguousarray(points)
+    if pts.dtype not in (np.float32, np.float64):
+        pts = pts.astype(np.float32)
+    dt = pts.dtype
+    n, rows = pts.shape
+    dd = 0 if descriptors is None else descriptors.shape[1]
+    desc = None if descriptors is None else np.ascontiguousarray(descriptors, dtype=dt)
+    of = np.empty((n, rows), dt)
+    od = np.empty((n, dd), dt)
+    no = C.c_int64(0)
+    rep = CovsReport()
+    X = None
+    if basis is not None:
+        X = np.ascontiguousarray(basis, dtype=np.float64)
+        if X.shape != (6, 6):
+            raise InvalidParameter("covariance_sampling: the basis must be (6, 6), column k the vector X_k")
+    l = lib()
+    rc = l.pmx_covariance_sampling(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n,
+                                   _ptr(desc) if dd else None, dd, int(normals_row), int(nb_sample), int(torque_norm),
+                                   _ptr(X) if X is not None else None, _ptr(of), _ptr(od) if dd else None,
+                                   C.byref(no), C.byref(rep))
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    report = dict(center=np.array(rep.center), lnorm=float(rep.lnorm), cov=np.array(rep.cov).reshape(6, 6),
+                  eigval=np.array(rep.eigval), eigvec=np.array(rep.eigvec).reshape(6, 6), depth=int(rep.depth))
+    return of[:no.value], od[:no.value], report
 
 
 def _float_array(a, dtype=None):

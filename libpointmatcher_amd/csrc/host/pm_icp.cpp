@@ -1501,6 +1501,54 @@ struct NormalSpaceDPF : PM<T>::DataPointsFilter {
     }
 };
 
+// CovarianceSamplingDataPointsFilter (DataPointsFilters/CovarianceSampling.h:
+// 70-76, CovarianceSampling.cpp:74-250) on the device (pmx_covariance_sampling,
+// pmx_covs.hip) with the library's own basis (include/pmx.h).  nbSample >= n
+// leaves the cloud as it is before the filter looks for normals (:81-86).
+// torqueNorm follows its documented meaning (0 L = 1, 1 Lavg, 2 Lmax): the
+// reference reads it with get<std::uint8_t>, i.e. as a character code, so no
+// branch of :115-133 matches there and L stays 1.
+template <typename T>
+struct CovarianceSamplingDPF : PM<T>::DataPointsFilter {
+    typedef Parametrizable P;
+    static Parametrizable::ParametersDoc doc() {
+        return {PDoc("nbSample", "Number of point to select.", "5000", "1", "4294967295", &P::Comp<std::size_t>),
+                PDoc("torqueNorm",
+                     "Method for torque normalization: (0) L=1 (no normalization, more t-normals), (1) L=Lavg "
+                     "(average distance, torque is scale-independent), (2) L=Lmax (scale in unit ball, more "
+                     "r-normals)",
+                     "1", "0", "2", &P::Comp<int>)};
+    }
+    const std::size_t nbSample;
+    const int torqueNorm;
+    explicit CovarianceSamplingDPF(const Parametrizable::Parameters& p)
+        : PM<T>::DataPointsFilter("CovarianceSamplingDataPointsFilter", doc(), p),
+          nbSample(this->template get<std::size_t>("nbSample")),
+          torqueNorm(this->template get<int>("torqueNorm")) {}
+    void inPlaceFilter(DataPoints<T>& cloud) override {
+        if (cloud.rows != 4)
+            throw InvalidParameter("CovarianceSamplingDataPointsFilter: 3-D clouds only (4 homogeneous rows)");
+        if (nbSample >= (std::size_t)cloud.n) return;  // :81
+        int off = 0, span = 0;
+        if (!descriptor_rows(cloud, "normals", off, span))  // :85-86 (the reference's text names OrientNormals)
+            throw InvalidField("CovarianceSamplingDataPointsFilter: Error, cannot find normals in descriptors.");
+        cloud.materialize();
+        const int64_t n = cloud.n;
+        std::vector<T> feat((size_t)(n * cloud.rows)), desc((size_t)(n * cloud.descDim));
+        int64_t nout = 0;
+        const int rc = pmx_covariance_sampling(this->device, dtype_of<T>(), cloud.features.data(), cloud.rows, n,
+                                               cloud.descriptors.data(), cloud.descDim, off, (int64_t)nbSample,
+                                               torqueNorm, nullptr, feat.data(), desc.data(), &nout, nullptr);
+        if (rc == PMX_E_BAD_PARAM) throw InvalidParameter(pmx_last_error(nullptr));
+        if (rc) throw std::runtime_error(std::string("CovarianceSamplingDataPointsFilter: ") + pmx_last_error(nullptr));
+        cloud.n = nout;
+        feat.resize((size_t)(nout * cloud.rows));
+        cloud.features.swap(feat);
+        desc.resize((size_t)(nout * cloud.descDim));
+        cloud.descriptors.swap(desc);
+    }
+};
+
 // ShadowDataPointsFilter (DataPointsFilters/Shadow.cpp:44-94, parameter
 // Shadow.h:60-65): keep |normalized(normal) . normalized(point)| > sin(eps);
 // the constructor takes the sine in T.
@@ -1997,6 +2045,8 @@ PointMatcher<T>::PointMatcher() {
                                   [](const Ps& p) { return std::make_shared<OctreeGridDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("NormalSpaceDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<NormalSpaceDPF<T>>(p); }, true);
+    DataPointsFilterRegistrar.reg("CovarianceSamplingDataPointsFilter",
+                                  [](const Ps& p) { return std::make_shared<CovarianceSamplingDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("SamplingSurfaceNormalDataPointsFilter",
                                   [](const Ps& p) { return std::make_shared<SamplingSurfaceNormalDPF<T>>(p); }, true);
     DataPointsFilterRegistrar.reg("ShadowDataPointsFilter",

@@ -4,6 +4,7 @@
 // device, each on a temporary context or stream (the self-match of the normals
 // uses the grid match).
 #include "pmx_ctx.h"
+#include "common/pmx_covs.h"
 #include "common/pmx_nss.h"
 
 namespace pmxc {
@@ -347,6 +348,94 @@ int nss_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int 
     if (hipStreamSynchronize(st) != hipSuccess) return PMX_E_HIP;
     *n_out = m;
     if (n_recheck) *n_recheck = rechecked;
+    return PMX_OK;
+}
+
+// CovarianceSamplingDataPointsFilter (pmx_covs.hip): the checks in the
+// reference's order (CovarianceSampling.cpp:77-86) with the early exit before
+// any look at the normals, then upload, the sampling and the download of the
+// nb_sample kept columns
+template <typename T>
+int covs_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int desc_dim, int normals_row,
+              int64_t nb_sample, int torque_norm, const double* basis, T* feat_out, T* desc_out, int64_t* n_out,
+              pmx_covs_report* report) {
+    const char* who = "CovarianceSamplingDataPointsFilter: ";
+    *n_out = 0;
+    if (report) *report = pmx_covs_report{};
+    if (rows != 4) {  // (:77 only asserts; a release build would read the homogeneous row as z)
+        g_err = std::string(who) + "3-D clouds only (4 homogeneous rows)";
+        return PMX_E_BAD_PARAM;
+    }
+    if (nb_sample < 1 || desc_dim < 0 || n < 0) {
+        g_err = std::string(who) + "nbSample must be >= 1, the point count and the descriptor dimension >= 0";
+        return PMX_E_BAD_PARAM;
+    }
+    if (torque_norm < 0 || torque_norm > 2) {
+        g_err = std::string(who) + "torqueNorm must be 0 (L = 1), 1 (L = Lavg) or 2 (L = Lmax)";
+        return PMX_E_BAD_PARAM;
+    }
+    if (n > (int64_t)0x7fffffff) {
+        g_err = std::string(who) + "more than 2^31 points";
+        return PMX_E_BAD_PARAM;
+    }
+    if (nb_sample >= n) {  // :81 (n = 0 included): the cloud as it is
+        if (n > 0) std::memcpy(feat_out, feat, sizeof(T) * (size_t)rows * n);
+        if (n > 0 && desc_dim > 0 && desc_out) std::memcpy(desc_out, desc, sizeof(T) * (size_t)desc_dim * n);
+        *n_out = n;
+        return PMX_OK;
+    }
+    if (normals_row < 0 || normals_row + 3 > desc_dim) {  // :85
+        g_err = std::string(who) + "the normals (3 rows from normals_row) are not rows of the descriptors";
+        return PMX_E_BAD_PARAM;
+    }
+    if (basis)
+        for (int a = 0; a < 36; ++a)
+            if (!covs_finite((T)basis[a])) {
+                g_err = std::string(who) + "the supplied basis has a non-finite entry";
+                return PMX_E_BAD_PARAM;
+            }
+    NssRandState rs;  // (the filter draws nothing; the GPU runtime does not leave the process's generator alone)
+    if (hipSetDevice(device) != hipSuccess) {
+        g_err = std::string(who) + "no HIP device";
+        return PMX_E_HIP;
+    }
+    hipStream_t st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return PMX_E_HIP;
+    std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> free_st(
+        st, [](hipStream_t s) { (void)hipStreamDestroy(s); });
+    const size_t fb = sizeof(T) * (size_t)rows * n, db = sizeof(T) * (size_t)desc_dim * n;
+    const size_t fa = (fb + 255) & ~(size_t)255, da = (db + 255) & ~(size_t)255;
+    const size_t ofb = sizeof(T) * (size_t)rows * nb_sample, odb = sizeof(T) * (size_t)desc_dim * nb_sample;
+    const size_t ofa = (ofb + 255) & ~(size_t)255;
+    char* buf = nullptr;
+    if (hipMalloc(&buf, fa + da + ofa + odb) != hipSuccess) {
+        g_err = std::string(who) + "device allocation failed";
+        return PMX_E_HIP;
+    }
+    std::unique_ptr<void, void (*)(void*)> free_buf(buf, [](void* p) { (void)hipFree(p); });
+    T* d_f = (T*)buf;
+    T* d_d = (T*)(buf + fa);
+    T* d_of = (T*)(buf + fa + da);
+    T* d_od = (T*)(buf + fa + da + ofa);
+    if (hipMemcpyAsync(d_f, feat, fb, hipMemcpyHostToDevice, st) != hipSuccess) return PMX_E_HIP;
+    if (hipMemcpyAsync(d_d, desc, db, hipMemcpyHostToDevice, st) != hipSuccess) return PMX_E_HIP;
+    std::string err;
+    int64_t m = 0;
+    pmx_covs_report rep;
+    const int rc = covs_run<T>(feat, desc, d_f, n, d_d, desc_dim, normals_row, nb_sample, torque_norm, basis, d_of,
+                               d_od, &m, rep, st, err);
+    if (rc) {
+        g_err = err.empty() ? std::string(who) + "HIP failure" : err;
+        return rc;
+    }
+    if (hipMemcpyAsync(feat_out, d_of, sizeof(T) * (size_t)rows * m, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return PMX_E_HIP;
+    if (desc_out &&
+        hipMemcpyAsync(desc_out, d_od, sizeof(T) * (size_t)desc_dim * m, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return PMX_E_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return PMX_E_HIP;
+    *n_out = m;
+    if (report) *report = rep;
     return PMX_OK;
 }
 
@@ -698,6 +787,25 @@ int pmx_normal_space(int device, int dtype, const void* feat, int rows, int64_t 
     if (dtype == PMX_F64)
         return nss_impl<double>(device, (const double*)feat, rows, n, (const double*)desc, desc_dim, normals_row,
                                 nb_sample, seed, epsilon, (double*)feat_out, (double*)desc_out, n_out, n_recheck);
+    g_err = "dtype must be PMX_F32 or PMX_F64";
+    return PMX_E_BAD_PARAM;
+}
+
+int pmx_covariance_sampling(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc,
+                            int desc_dim, int normals_row, int64_t nb_sample, int torque_norm, const double* basis,
+                            void* feat_out, void* desc_out, int64_t* n_out, pmx_covs_report* report) {
+    // (n beyond the contract is refused by the checks before anything is read)
+    const bool sized = n > 0 && n <= (int64_t)0x7fffffff;
+    if (!n_out || (sized && (!feat || !feat_out || (desc_dim > 0 && (!desc || !desc_out))))) {
+        g_err = "null argument";
+        return PMX_E_BAD_PARAM;
+    }
+    if (dtype == PMX_F32)
+        return covs_impl<float>(device, (const float*)feat, rows, n, (const float*)desc, desc_dim, normals_row,
+                                nb_sample, torque_norm, basis, (float*)feat_out, (float*)desc_out, n_out, report);
+    if (dtype == PMX_F64)
+        return covs_impl<double>(device, (const double*)feat, rows, n, (const double*)desc, desc_dim, normals_row,
+                                 nb_sample, torque_norm, basis, (double*)feat_out, (double*)desc_out, n_out, report);
     g_err = "dtype must be PMX_F32 or PMX_F64";
     return PMX_E_BAD_PARAM;
 }

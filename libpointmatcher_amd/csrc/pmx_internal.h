@@ -26,6 +26,8 @@
 #include "pmx_match_plan.h"
 #include "pmx_sums.h"
 
+struct pmx_covs_report;  // include/pmx.h (what pmx_covariance_sampling reports)
+
 namespace pmx {
 
 template <typename T>
@@ -365,6 +367,16 @@ template <typename T>
 int nss_run(const T* h_desc, const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int nrow,
             int64_t nb_sample, uint64_t seed, T eps, T* d_of, T* d_od, int64_t* n_out, int64_t* n_recheck,
             NssRandState& rs, hipStream_t st, std::string& err);
+// CovarianceSamplingDataPointsFilter (pmx_covs.hip; the parameters:
+// pmx_covariance_sampling of include/pmx.h) past the reference's early exits
+// (rows 4, 1 <= nb_sample < n < 2^31, torque_norm in 0..2, nrow + 3 <= desc_dim,
+// basis null or finite).  h_f / h_desc: the host's cloud (the picked points'
+// projections are evaluated from it); the rest device in / out, capacity
+// nb_sample.  rep: what the call reports, zeroed first.
+template <typename T>
+int covs_run(const T* h_f, const T* h_desc, const T* d_f, int64_t n, const T* d_desc, int desc_dim, int nrow,
+             int64_t nb_sample, int torque_norm, const double* basis, T* d_of, T* d_od, int64_t* n_out,
+             ::pmx_covs_report& rep, hipStream_t st, std::string& err);
 // IncidenceAngle, Sphericality and RemoveSensorBias (pmx_sensor.hip); device
 // pointers, point-major.  sensor_bias_run: d_cf is scratch of rows x n for the
 // corrected features; outputs of capacity n.  sensor_bias_check: its parameter
