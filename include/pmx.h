@@ -48,6 +48,10 @@
  *                         getOverlap (PointMatcher.h:552-554; PointToPlane.cpp:
  *                         316-465, PointToPoint.cpp:104-164), with
  *                         pmx_set_reading_noise / pmx_set_reference_descriptors
+ *   pmx_error_elements_prepare / pmx_error_elements /
+ *   pmx_loop_error_elements_prepare
+ *                       ErrorMinimizer::getErrorElements (PointMatcher.h:549-551,
+ *                         ErrorMinimizer.cpp:58-193): the kept pairs themselves
  *   pmx_get_matches /   lazy host mirrors of Matches / OutlierWeights for
  *   pmx_get_weights       CPU modules and inspectors (PointMatcher.h:371-391)
  *
@@ -404,6 +408,50 @@ typedef struct pmx_quality {
     int branch;
 } pmx_quality;
 int pmx_match_quality(pmx_ctx* ctx, const void* T_step, int minimizer, pmx_quality* out);
+/* ErrorMinimizer::getErrorElements (PointMatcher.h:549-551, ErrorMinimizer.cpp:
+ * 58-193) for the last pmx_match and its recorded filter chain: the kept pairs
+ * as columns, compacted on the device.  A column is an entry (i, s) with
+ * dist != inf && w != 0, i the reading index (this rank's shard) rising and s
+ * the link rank 0..k-1 rising within i (ErrorMinimizer.cpp:98-135); w is the
+ * chain's weight as pmx_get_weights returns it, so a negative weight is a
+ * column and a zero one is not.
+ * pmx_error_elements_prepare flags, scans and compacts into buffers the
+ * context owns and returns the counts of this rank's shard: columns,
+ * rejected_matches (entries with dist != inf and w == 0) and rejected_points
+ * (reading points without a kept entry).  T_step (rows x rows row-major T;
+ * NULL: the match's own T_iter) transforms the reading.  PMX_E_STATE without a
+ * match; PMX_E_NO_POINTS when no column exists (the counts are still returned;
+ * the reference throws "no point to minimize", :76-77); PMX_E_EMPTY_QUANTILE
+ * as the system calls return it; PMX_E_BAD_PARAM beyond 2^31 - 1 entries.
+ * pmx_error_elements copies the prepared columns out (P = columns, point-major;
+ * every pointer may be NULL):
+ *   reading        rows x P T: the step reading point, each row ((m0 x + m1 y) +
+ *                  m2 z) + m3 h separately rounded, the homogeneous row the
+ *                  resident point's own; a 2-D context has rows = 3 (x, y, h)
+ *   reference      rows x P T: the matched reference point as the context holds
+ *                  it (the centred frame of pmx_set_reference_centred)
+ *   ref_normals    (rows - 1) x P T: its normal; PMX_E_BAD_PARAM on a reference
+ *                  without normals
+ *   dists, weights P T: the entry's squared distance and chain weight
+ *   ids            P int32: the original reference index
+ *   reading_index, link_rank
+ *                  P int32: i (shard-local) and s
+ * PMX_E_STATE without a prepare, or once a new match, filter call, reading,
+ * reading normals or radii, or reference (descriptor) has made the prepared
+ * columns stale.  The buffers are reused by the next prepare and freed with the
+ * context.  No collective: every rank returns its shard's columns, and the
+ * ranks' columns in rank order are the single-process columns.  Both calls
+ * synchronise the stream; neither belongs inside an iteration. */
+typedef struct pmx_elements_info {
+    int64_t columns, rejected_matches, rejected_points;
+} pmx_elements_info;
+/* The step transform of the last match (rows x rows row-major T): pmx_match's
+ * T_iter, or after a finished device loop the transform its last match ran at.
+ * PMX_E_STATE without a match. */
+int pmx_get_step_transform(pmx_ctx* ctx, void* T_step);
+int pmx_error_elements_prepare(pmx_ctx* ctx, const void* T_step, pmx_elements_info* info);
+int pmx_error_elements(pmx_ctx* ctx, void* reading, void* reference, void* ref_normals, void* dists, int32_t* ids,
+                       void* weights, int32_t* reading_index, int32_t* link_rank);
 
 /* ---------------------------------------------------------- host mirrors --- */
 /* dists: k x N T (point-major), ids: k x N int32 (this rank's shard) */
@@ -516,6 +564,9 @@ int pmx_loop_covariance(pmx_ctx* ctx, double* H, double* Q, int64_t* pairs);
  * device.  PMX_E_STATE before a loop has finished or after one that stopped on
  * an error. */
 int pmx_loop_quality(pmx_ctx* ctx, int minimizer, pmx_quality* out);
+/* pmx_error_elements_prepare for a finished loop: its last match and step
+ * transform, as pmx_loop_quality; pmx_error_elements then copies the columns. */
+int pmx_loop_error_elements_prepare(pmx_ctx* ctx, pmx_elements_info* info);
 /* T_iter after each completed iteration (keep_trace): count x rows x rows T */
 int pmx_loop_trace(pmx_ctx* ctx, int first, int count, void* out);
 /* Quantile window statistics of the device loop (no reference counterpart;

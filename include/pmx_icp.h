@@ -132,6 +132,47 @@ int pmx_icp_covariance(pmx_icp* icp, void* cov36);
  * text (PointToPlane.cpp:384).  A multi-rank ICP calls them on every rank. */
 int pmx_icp_overlap(pmx_icp* icp, double* overlap);
 int pmx_icp_residual_error(pmx_icp* icp, double* residual);
+/* errorMinimizer->getErrorElements() (PointMatcher.h:549-551, ErrorMinimizer.cpp:
+ * 58-193): the pairs the last iteration of the last compute kept, one column
+ * per pair, the reading index rising and the link rank rising within it.
+ * Lazy like the two calls above: the first call after a checker stopped the ICP
+ * compacts the match still resident on the device (pmx_error_elements_prepare /
+ * pmx_loop_error_elements_prepare, include/pmx.h, by the path that ran), then
+ * the result is cached until the next prepare / set_map; an ICP that never
+ * asks launches and retains nothing.  Before any compute: zero columns and no
+ * error (the reference's default-constructed lastErrorElements).  A chain that
+ * kept nothing: PMX_ICP_CONVERGENCE_ERROR.  A multi-rank ICP returns its shard.
+ *   pmx_icp_error_elements_info        columns, rows, the two descriptor
+ *                                      dimensions and the rejected counts
+ *   pmx_icp_error_elements             columns <= capacity (else
+ *                                      PMX_ICP_INVALID_PARAMETER); any pointer may
+ *                                      be NULL: reading / reference rows x P T
+ *                                      (point-major, the reference's centred
+ *                                      frame), dists, weights P T, ids (into the
+ *                                      filtered reference), reading_index (into
+ *                                      the filtered reading) P int32
+ *   pmx_icp_error_elements_descriptor  one labelled descriptor of the columns,
+ *                                      span x P T into out (capacity in
+ *                                      values; out NULL: only *span, 0 when the
+ *                                      cloud has no such descriptor); cloud 0
+ *                                      reading, 1 reference
+ * The descriptors are gathered from the filtered clouds of the last prepare
+ * (with readingStepDataPointsFilters the last iteration's step reading; for a
+ * sequence the held map); the reading's "normals" and "observationDirections"
+ * are rotated by T_refMean_dataIn and the last match's T_iter, each component
+ * (m0 n0 + m1 n1) + m2 n2 in T.  Arrays passed by pointer to prepare / compute
+ * without a data filter on their side (the reference's normals) are read in
+ * place at the first call: keep them valid until then. */
+typedef struct pmx_icp_elements_info {
+    int64_t columns;
+    int rows, reading_desc_dim, reference_desc_dim;
+    int64_t rejected_matches, rejected_points;
+} pmx_icp_elements_info;
+int pmx_icp_error_elements_info(pmx_icp* icp, pmx_icp_elements_info* info);
+int pmx_icp_error_elements(pmx_icp* icp, int64_t capacity, void* reading, void* reference, void* dists, int32_t* ids,
+                           void* weights, int32_t* reading_index);
+int pmx_icp_error_elements_descriptor(pmx_icp* icp, int cloud, const char* name, void* out, int64_t capacity,
+                                      int* span);
 /* Inspection: the descriptor `name` of a cloud (rows x n, T) after the chain's
  * readingDataPointsFilters (cloud 0) or referenceDataPointsFilters (cloud 1),
  * with the descriptors staged for that cloud.  *n_out the filtered point count,

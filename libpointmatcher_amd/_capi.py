@@ -155,6 +155,24 @@ class Quality(C.Structure):
                 ("links", C.c_int64), ("dist_sum", C.c_double), ("median_density", C.c_double), ("branch", C.c_int)]
 
 
+class ElementsInfo(C.Structure):
+    """pmx_elements_info (include/pmx.h): the counts of a prepared getErrorElements."""
+    _fields_ = [("columns", C.c_int64), ("rejected_matches", C.c_int64), ("rejected_points", C.c_int64)]
+
+
+class ErrorElements:
+    """ErrorMinimizer::getErrorElements' columns as numpy arrays (pmx_error_elements):
+    reading / reference (P, rows), ref_normals (P, rows - 1) or None, dists, weights
+    (P,), ids, reading_index, link_rank (P,) int32, and the two rejected counts."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def columns(self):
+        return len(self.dists)
+
+
 FORCE_KIND = {None: 0, "none": 0, "2D": 1, "4DOF": 2}  # PMX_FORCE_*
 
 MINIMIZER_KIND = {"PointToPlaneErrorMinimizer": 0, "PointToPointErrorMinimizer": 1,
@@ -169,7 +187,8 @@ EXPORTS = [
     "pmx_outlier_mediandist", "pmx_outlier_trimmed", "pmx_outlier_vartrimmed", "pmx_outlier_robust",
     "pmx_robust_scale", "pmx_set_reading_radii", "pmx_set_reading_normals", "pmx_outlier_surface_normal",
     "pmx_set_reference_weight_descriptor", "pmx_outlier_generic_descriptor",
-    "pmx_p2plane_system", "pmx_p2plane_system_forced", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
+    "pmx_p2plane_system", "pmx_p2plane_system_forced", "pmx_p2point_system", "pmx_p2point_similarity_system", "pmx_p2plane_covariance", "pmx_loop_covariance", "pmx_set_reading_noise", "pmx_set_reference_descriptors", "pmx_match_quality", "pmx_loop_quality",
+    "pmx_get_step_transform", "pmx_error_elements_prepare", "pmx_error_elements", "pmx_loop_error_elements_prepare", "pmx_get_matches", "pmx_get_weights", "pmx_vartrim_partial_sums",
     "pmx_get_shape", "pmx_grid_level_records", "pmx_timing_enable", "pmx_timing_read", "pmx_sync",
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter", "pmx_octree_grid",
@@ -229,6 +248,10 @@ def lib():
         l.pmx_set_reference_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         l.pmx_match_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Quality)]
         l.pmx_loop_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(Quality)]
+        l.pmx_get_step_transform.argtypes = [C.c_void_p, C.c_void_p]
+        l.pmx_error_elements_prepare.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ElementsInfo)]
+        l.pmx_error_elements.argtypes = [C.c_void_p] * 9
+        l.pmx_loop_error_elements_prepare.argtypes = [C.c_void_p, C.POINTER(ElementsInfo)]
         l.pmx_get_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         l.pmx_get_weights.argtypes = [C.c_void_p, C.c_void_p]
         l.pmx_vartrim_partial_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
@@ -891,6 +914,35 @@ class Context:
         q = Quality()
         self._chk(self._l.pmx_loop_quality(self.h, MINIMIZER_KIND[minimizer], C.byref(q)))
         return q
+
+    def _fetch_elements(self, info, normals):
+        P, r = info.columns, self.rows
+        e = ErrorElements(reading=np.empty((P, r), self.dtype), reference=np.empty((P, r), self.dtype),
+                          ref_normals=np.empty((P, r - 1), self.dtype) if normals else None,
+                          dists=np.empty(P, self.dtype), ids=np.empty(P, np.int32), weights=np.empty(P, self.dtype),
+                          reading_index=np.empty(P, np.int32), link_rank=np.empty(P, np.int32),
+                          rejected_matches=info.rejected_matches, rejected_points=info.rejected_points)
+        self._chk(self._l.pmx_error_elements(self.h, _ptr(e.reading), _ptr(e.reference),
+                                             _ptr(e.ref_normals) if normals else None, _ptr(e.dists), _ptr(e.ids),
+                                             _ptr(e.weights), _ptr(e.reading_index), _ptr(e.link_rank)))
+        return e
+
+    def error_elements(self, T_step=None, normals=None):
+        """getErrorElements of the last match (pmx_error_elements_prepare, then
+        pmx_error_elements).  T_step None: the match's own transform; normals
+        None: the reference's normals when it has them."""
+        info = ElementsInfo()
+        T = self._arr(T_step) if T_step is not None else None
+        self.last_elements_info = info  # (the counts come back with PMX_E_NO_POINTS too)
+        self._chk(self._l.pmx_error_elements_prepare(self.h, _ptr(T), C.byref(info)))
+        return self._fetch_elements(info, self._ref_keep[1] is not None if normals is None else normals)
+
+    def loop_error_elements(self, normals=None):
+        """The same for the last iteration of a finished device loop (pmx_loop_error_elements_prepare)."""
+        info = ElementsInfo()
+        self.last_elements_info = info
+        self._chk(self._l.pmx_loop_error_elements_prepare(self.h, C.byref(info)))
+        return self._fetch_elements(info, self._ref_keep[1] is not None if normals is None else normals)
 
     def get_matches(self):
         d = np.empty((self.N, self.knn), self.dtype)

@@ -119,11 +119,13 @@ std::vector<T> init_of(const void* T_init, int rows) {
 template <typename T>
 void prepare_impl(pmx_icp* icp, const void* reading, int rows, int64_t N, const void* reference, int64_t M,
                   const void* nrm, const void* T_init) {
-    auto rd = make_cloud<T>(reading, rows, N, nullptr);
-    auto ref = make_cloud<T>(reference, rows, M, nrm);
-    take_staged<T>(icp, 0, rd);
-    take_staged<T>(icp, 1, ref);
-    get<T>(icp).prepare(rd, ref, init_of<T>(T_init, rows));
+    // (shared with the chain: getErrorElements gathers the descriptors later;
+    // the staged ones are owned, the caller's arrays stay borrowed)
+    auto rd = std::make_shared<DataPoints<T>>(make_cloud<T>(reading, rows, N, nullptr));
+    auto ref = std::make_shared<DataPoints<T>>(make_cloud<T>(reference, rows, M, nrm));
+    take_staged<T>(icp, 0, *rd);
+    take_staged<T>(icp, 1, *ref);
+    get<T>(icp).prepare(std::move(rd), std::move(ref), init_of<T>(T_init, rows));
 }
 
 template <typename T>
@@ -148,9 +150,9 @@ void get_map_impl(pmx_icp* icp, void* feat, int64_t capacity, int64_t* n, int* r
 // 1: prepared (iterate / finish follow), 0: no map (T_out = identity)
 template <typename T>
 int seq_prepare_impl(pmx_icp* icp, const void* reading, int rows, int64_t N, const void* T_init) {
-    auto rd = make_cloud<T>(reading, rows, N, nullptr);
-    take_staged<T>(icp, 0, rd);
-    return get<T>(icp).prepareSequence(rd, init_of<T>(T_init, rows)) ? 1 : 0;
+    auto rd = std::make_shared<DataPoints<T>>(make_cloud<T>(reading, rows, N, nullptr));
+    take_staged<T>(icp, 0, *rd);
+    return get<T>(icp).prepareSequence(std::move(rd), init_of<T>(T_init, rows)) ? 1 : 0;
 }
 
 template <typename T>
@@ -172,6 +174,52 @@ double quality_impl(pmx_icp* icp, bool overlap) {
     auto& I = get<T>(icp);
     if (!I.errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
     return overlap ? (double)I.errorMinimizer->getOverlap() : (double)I.errorMinimizer->getResidualError();
+}
+
+template <typename T>
+const typename PointMatcher<T>::ErrorMinimizer::ErrorElements& elements_of(pmx_icp* icp) {
+    auto& I = get<T>(icp);
+    if (!I.errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
+    return I.errorMinimizer->getErrorElements();
+}
+
+template <typename T>
+void elements_info_impl(pmx_icp* icp, pmx_icp_elements_info* info) {
+    const auto& e = elements_of<T>(icp);
+    info->columns = (int64_t)e.dists.size();
+    info->rows = e.reading.rows;
+    info->reading_desc_dim = e.reading.descDim;
+    info->reference_desc_dim = e.reference.descDim;
+    info->rejected_matches = e.nbRejectedMatches;
+    info->rejected_points = e.nbRejectedPoints;
+}
+
+template <typename T>
+void elements_impl(pmx_icp* icp, int64_t capacity, void* reading, void* reference, void* dists, int32_t* ids,
+                   void* weights, int32_t* reading_index) {
+    const auto& e = elements_of<T>(icp);
+    const size_t P = e.dists.size();
+    if (capacity < 0 || (uint64_t)capacity < (uint64_t)P)
+        throw InvalidParameter("pmx_icp_error_elements: capacity below the number of columns");
+    if (reading) std::memcpy(reading, e.reading.features.data(), sizeof(T) * e.reading.features.size());
+    if (reference) std::memcpy(reference, e.reference.features.data(), sizeof(T) * e.reference.features.size());
+    if (dists) std::memcpy(dists, e.dists.data(), sizeof(T) * P);
+    if (weights) std::memcpy(weights, e.weights.data(), sizeof(T) * P);
+    if (ids) std::memcpy(ids, e.ids.data(), sizeof(int32_t) * P);
+    if (reading_index) std::memcpy(reading_index, e.readingIndex.data(), sizeof(int32_t) * P);
+}
+
+template <typename T>
+void elements_descriptor_impl(pmx_icp* icp, int cloud, const char* name, void* out, int64_t capacity, int* span) {
+    const auto& e = elements_of<T>(icp);
+    const DataPoints<T>& c = cloud == 0 ? e.reading : e.reference;
+    *span = 0;
+    if (!c.descriptorExists(name)) return;
+    const std::vector<T> v = c.descriptor(name, span);
+    if (!out) return;
+    if (capacity < 0 || (uint64_t)capacity < (uint64_t)v.size())
+        throw InvalidParameter("pmx_icp_error_elements_descriptor: capacity below columns * span");
+    std::memcpy(out, v.data(), sizeof(T) * v.size());
 }
 
 // one chain of data filters applied to a copy of the caller's cloud
@@ -409,6 +457,30 @@ int pmx_icp_covariance(pmx_icp* icp, void* cov36) {
 int pmx_icp_overlap(pmx_icp* icp, double* overlap) {
     if (!icp || !overlap) return PMX_ICP_INVALID_PARAMETER;
     return guarded(icp, [&] { *overlap = BOTH(icp, quality_impl<float>(icp, true), quality_impl<double>(icp, true)); });
+}
+
+int pmx_icp_error_elements_info(pmx_icp* icp, pmx_icp_elements_info* info) {
+    if (!icp || !info) return PMX_ICP_INVALID_PARAMETER;
+    std::memset(info, 0, sizeof(*info));
+    return guarded(icp, [&] { BOTH(icp, elements_info_impl<float>(icp, info), elements_info_impl<double>(icp, info)); });
+}
+
+int pmx_icp_error_elements(pmx_icp* icp, int64_t capacity, void* reading, void* reference, void* dists, int32_t* ids,
+                           void* weights, int32_t* reading_index) {
+    if (!icp) return PMX_ICP_INVALID_PARAMETER;
+    return guarded(icp, [&] {
+        BOTH(icp, elements_impl<float>(icp, capacity, reading, reference, dists, ids, weights, reading_index),
+             elements_impl<double>(icp, capacity, reading, reference, dists, ids, weights, reading_index));
+    });
+}
+
+int pmx_icp_error_elements_descriptor(pmx_icp* icp, int cloud, const char* name, void* out, int64_t capacity,
+                                      int* span) {
+    if (!icp || !name || !span || (cloud != 0 && cloud != 1)) return PMX_ICP_INVALID_PARAMETER;
+    return guarded(icp, [&] {
+        BOTH(icp, elements_descriptor_impl<float>(icp, cloud, name, out, capacity, span),
+             elements_descriptor_impl<double>(icp, cloud, name, out, capacity, span));
+    });
 }
 
 int pmx_icp_residual_error(pmx_icp* icp, double* residual) {

@@ -2217,9 +2217,23 @@ static double since(const std::chrono::steady_clock::time_point& t) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
 }
 
+// a caller's cloud as a shared pointer that owns nothing (the caller keeps it alive)
+template <typename C>
+static std::shared_ptr<const C> borrowed_cloud(const C& c) {
+    return std::shared_ptr<const C>(std::shared_ptr<const C>(), &c);
+}
+
 template <typename T>
 void PointMatcher<T>::ICP::prepare(const DataPoints& readingIn, const DataPoints& referenceIn,
                                    const TransformationParameters& T_init) {
+    prepare(borrowed_cloud(readingIn), borrowed_cloud(referenceIn), T_init);
+}
+
+template <typename T>
+void PointMatcher<T>::ICP::prepare(std::shared_ptr<const DataPoints> readingPtr,
+                                   std::shared_ptr<const DataPoints> referencePtr,
+                                   const TransformationParameters& T_init) {
+    const DataPoints& referenceIn = *referencePtr;
     // ICP::compute, ICP.cpp:265-313
     if (!matcher) throw std::runtime_error("You must setup a matcher before running ICP");
     if (!errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
@@ -2239,13 +2253,14 @@ void PointMatcher<T>::ICP::prepare(const DataPoints& readingIn, const DataPoints
     // (no reference filters: the caller's cloud is uploaded as it is and
     // centred on the device — no host copy of the reference)
     const bool filtered = !referenceDataPointsFilters.empty();
-    DataPoints refCopy;
-    if (filtered) {
-        refCopy = referenceIn;
+    if (filtered) {  // (the one filtered copy, kept for getErrorElements' gathers)
+        auto refCopy = std::make_shared<DataPoints>(referenceIn);
         referenceDataPointsFilters.init();
-        referenceDataPointsFilters.apply(refCopy);
+        referenceDataPointsFilters.apply(*refCopy);
+        referencePtr = std::move(refCopy);
     }
-    const DataPoints& reference = filtered ? refCopy : referenceIn;
+    const DataPoints& reference = *referencePtr;
+    elemReference_.reset();
     const int64_t M = reference.n;
     if (M <= 0) throw ConvergenceError("empty reference");
     // mean of the reference columns in T, ICP.cpp:291-292 (each coordinate's
@@ -2262,13 +2277,16 @@ void PointMatcher<T>::ICP::prepare(const DataPoints& readingIn, const DataPoints
     for (int r = 0; r < dim - 1; ++r) T_refIn_refMean_[r * dim + dim - 1] = mean[r];
     referencePreprocessingDuration = since<T>(t);
     prefilteredReferencePtsCount = M;
-    prepareReading(readingIn, T_init);
+    elemReference_ = std::move(referencePtr);
+    prepareReading(std::move(readingPtr), T_init);
 }
 
 // computeWithTransformedReference up to the loop, ICP.cpp:317-370
 // (T_refIn_refMean_ and the matcher describe the reference)
 template <typename T>
-void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const TransformationParameters& T_init) {
+void PointMatcher<T>::ICP::prepareReading(std::shared_ptr<const DataPoints> readingPtr,
+                                          const TransformationParameters& T_init) {
+    const DataPoints& readingIn = *readingPtr;
     const int dim = (int)std::lround(std::sqrt((double)T_refIn_refMean_.size()));
     if ((int64_t)T_init.size() != (int64_t)dim * dim)
         throw std::runtime_error("The shape of initial transformation matrix must be NxN. Where N is the number of "
@@ -2276,13 +2294,15 @@ void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const Tra
     if (readingIn.rows != dim) throw std::runtime_error("reading and reference dimensions differ");
     const auto t = std::chrono::steady_clock::now();
     // (no reading filters: the caller's cloud directly, no host copy)
-    DataPoints readCopy;
-    if (!readingDataPointsFilters.empty()) {
-        readCopy = readingIn;
+    if (!readingDataPointsFilters.empty()) {  // (the one filtered copy, kept for getErrorElements' gathers)
+        auto readCopy = std::make_shared<DataPoints>(readingIn);
         readingDataPointsFilters.init();
-        readingDataPointsFilters.apply(readCopy);
+        readingDataPointsFilters.apply(*readCopy);
+        readingPtr = std::move(readCopy);
     }
-    const DataPoints& reading = readingDataPointsFilters.empty() ? readingIn : readCopy;
+    const DataPoints& reading = *readingPtr;
+    elemReading_ = readingPtr;
+    elemStep_ = elemNormalsPre_ = false;
     // T_refMean_dataIn = T_refIn_refMean^-1 * T_init (the inverse of a pure
     // translation is exact), ICP.cpp:345-346
     TransformationParameters inv((size_t)dim * dim, (T)0);
@@ -2301,6 +2321,7 @@ void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const Tra
     uploadReadingNormals(reading);       // (SurfaceNormalOutlierFilter; rotated by T_refMean_dataIn on the device)
     keepReadingNoise(reading);
     errorMinimizer->quality_.stopped = errorMinimizer->quality_.valid = false;  // (a new compute: the cache goes)
+    errorMinimizer->elements_ = typename ErrorMinimizer::Elements();
     // readingStepDataPointsFilters (ICP.cpp:349-350, 373-377): the step
     // filters see the reading in <refMean> every iteration; keep that copy on
     // the host (the device's transform, restated: the same separately rounded
@@ -2341,6 +2362,7 @@ void PointMatcher<T>::ICP::prepareReading(const DataPoints& readingIn, const Tra
                     for (int r = 0; r < D; ++r) v[r] = o[r];
                 }
                 stepBase_.setDescriptor("normals", span, nr.data());
+                elemNormalsPre_ = true;
             }
         }
         for (auto& f : readingStepDataPointsFilters) f->device = dev.device;
@@ -2403,6 +2425,8 @@ bool PointMatcher<T>::ICP::setMap(const DataPoints& inputCloud) {
     matcher->init(dev, map);  // ICP.cpp:503 (the grid stays on the device)
     keepReferenceDescriptors(map);
     if (errorMinimizer) errorMinimizer->quality_.stopped = errorMinimizer->quality_.valid = false;
+    if (errorMinimizer) errorMinimizer->elements_ = typename ErrorMinimizer::Elements();
+    elemReference_.reset();
     map_ = std::move(map);
     T_map_ = std::move(T_map);
     mapIndexed_ = true;
@@ -2413,6 +2437,8 @@ bool PointMatcher<T>::ICP::setMap(const DataPoints& inputCloud) {
 
 template <typename T>
 void PointMatcher<T>::ICP::clearMap() {
+    if (errorMinimizer) errorMinimizer->elements_ = typename ErrorMinimizer::Elements();
+    elemReference_.reset();
     map_ = DataPoints();
     T_map_.clear();
     mapIndexed_ = false;
@@ -2442,6 +2468,12 @@ void PointMatcher<T>::ICP::reinitMap() {
 
 template <typename T>
 bool PointMatcher<T>::ICP::prepareSequence(const DataPoints& readingIn, const TransformationParameters& T_init) {
+    return prepareSequence(borrowed_cloud(readingIn), T_init);
+}
+
+template <typename T>
+bool PointMatcher<T>::ICP::prepareSequence(std::shared_ptr<const DataPoints> readingIn,
+                                           const TransformationParameters& T_init) {
     if (!hasMap()) return false;  // "Ignoring attempt to perform ICP with an empty map"
     if (!matcher) throw std::runtime_error("You must setup a matcher before running ICP");
     if (!errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
@@ -2459,7 +2491,8 @@ bool PointMatcher<T>::ICP::prepareSequence(const DataPoints& readingIn, const Tr
     for (auto& f : readingDataPointsFilters) f->device = dev.device;
     if (!mapIndexed_) reinitMap();  // (a plain compute replaced the device's reference)
     T_refIn_refMean_ = T_map_;
-    prepareReading(readingIn, T_init);
+    elemReference_ = borrowed_cloud(map_);  // (the held map: dropped by setMap / clearMap)
+    prepareReading(std::move(readingIn), T_init);
     return true;
 }
 
@@ -2533,6 +2566,98 @@ void PointMatcher<T>::ICP::stopped(bool deviceLoop) {
     q.readingNoise = rdNoise_;
     q.refNoise = refNoise_;
     q.refDens = refDens_;
+    auto& e = errorMinimizer->elements_;
+    e = typename ErrorMinimizer::Elements();
+    e.dev = &dev;
+    e.stopped = true;
+    e.loop = deviceLoop;
+    e.reading = elemReading_;
+    e.reference = elemReference_;
+    e.T_pre = T_refMean_dataIn_;
+    e.normalsPre = elemStep_ && elemNormalsPre_;
+    e.rows = rows_;
+}
+
+// every descriptor of src's points idx[0, P), point-major, into dst
+template <typename T>
+static void gather_descriptors(const DataPoints<T>& src, const std::vector<int32_t>& idx, DataPoints<T>& dst) {
+    dst.descriptorLabels = src.descriptorLabels;
+    dst.descDim = src.descDim;
+    dst.descriptors.resize((size_t)src.descDim * idx.size());
+    const T* d = src.desc();
+    for (size_t j = 0; j < idx.size(); ++j) {
+        if (idx[j] < 0 || (int64_t)idx[j] >= src.n)
+            throw std::runtime_error("getErrorElements: a column's index lies outside the filtered cloud");
+        std::memcpy(&dst.descriptors[j * src.descDim], d + (size_t)idx[j] * src.descDim, sizeof(T) * src.descDim);
+    }
+}
+
+// the rotation block of M (rows x rows) applied to the D-vectors of descriptor
+// `name`, each component (m0 n0 + m1 n1) + m2 n2 in T (TransformationsImpl.cpp:72-84)
+template <typename T>
+static void rotate_descriptor(DataPoints<T>& c, const char* name, const T* M, int rows) {
+    const int D = rows - 1;
+    int off = 0;
+    for (auto& l : c.descriptorLabels) {
+        if (l.text == name && l.span == D) {
+            for (int64_t j = 0; j < c.n; ++j) {
+                T* v = &c.descriptors[(size_t)j * c.descDim + off];
+                T o[3] = {0, 0, 0};
+                for (int r = 0; r < D; ++r) {
+                    T s = M[r * rows + 0] * v[0] + M[r * rows + 1] * v[1];
+                    if (D == 3) s = s + M[r * rows + 2] * v[2];
+                    o[r] = s;
+                }
+                for (int r = 0; r < D; ++r) v[r] = o[r];
+            }
+            return;
+        }
+        off += l.span;
+    }
+}
+
+template <typename T>
+const typename PointMatcher<T>::ErrorMinimizer::ErrorElements& PointMatcher<T>::ErrorMinimizer::getErrorElements()
+    const {
+    Elements& s = elements_;
+    if (!s.stopped || !s.dev || s.valid) return s.e;  // (empty before any compute)
+    const Device& d = *s.dev;
+    pmx_elements_info info;
+    d.check(s.loop ? pmx_loop_error_elements_prepare(d.ctx, &info) : pmx_error_elements_prepare(d.ctx, nullptr, &info));
+    const size_t P = (size_t)info.columns;
+    const int rows = s.rows;
+    ErrorElements e;
+    e.reading.rows = e.reference.rows = rows;
+    e.reading.n = e.reference.n = (int64_t)P;
+    e.reading.features.resize(P * rows);
+    e.reference.features.resize(P * rows);
+    e.dists.resize(P);
+    e.weights.resize(P);
+    e.ids.resize(P);
+    e.readingIndex.resize(P);
+    d.check(pmx_error_elements(d.ctx, e.reading.features.data(), e.reference.features.data(), nullptr, e.dists.data(),
+                               e.ids.data(), e.weights.data(), e.readingIndex.data(), nullptr));
+    std::vector<T> Tm((size_t)rows * rows);
+    d.check(pmx_get_step_transform(d.ctx, Tm.data()));
+    e.nbRejectedMatches = info.rejected_matches;
+    e.nbRejectedPoints = info.rejected_points;
+    if (s.reading) {
+        e.reading.featureLabels = s.reading->featureLabels;
+        gather_descriptors<T>(*s.reading, e.readingIndex, e.reading);
+        for (const char* name : {"normals", "observationDirections"}) {
+            // (a step reading's normals may already carry T_refMean_dataIn's rotation: prepareReading)
+            if (!(s.normalsPre && std::string(name) == "normals"))
+                rotate_descriptor<T>(e.reading, name, s.T_pre.data(), rows);
+            rotate_descriptor<T>(e.reading, name, Tm.data(), rows);
+        }
+    }
+    if (s.reference) {
+        e.reference.featureLabels = s.reference->featureLabels;
+        gather_descriptors<T>(*s.reference, e.ids, e.reference);
+    }
+    s.e = std::move(e);
+    s.valid = true;
+    return s.e;
 }
 
 template <typename T>
@@ -2648,8 +2773,11 @@ bool PointMatcher<T>::ICP::stepModules() {
         std::fabs((T)1 - dense::det_rot(T_iter_.data(), dim)) > (T)0.001)  // TransformationsImpl.cpp:62-63
         throw TransformationError("RigidTransformation: Error, rotation matrix is not orthogonal.");
     if (!readingStepDataPointsFilters.empty()) {  // ICP.cpp:373-377
-        DataPoints stepReading(stepBase_);
+        auto stepPtr = std::make_shared<DataPoints>(stepBase_);
+        DataPoints& stepReading = *stepPtr;
         readingStepDataPointsFilters.apply(stepReading);
+        elemReading_ = stepPtr;  // (the last iteration's is the one getErrorElements gathers from)
+        elemStep_ = true;
         TransformationParameters I((size_t)dim * dim, (T)0);
         for (int i = 0; i < dim; ++i) I[(size_t)i * dim + i] = 1;
         dev.check(pmx_set_reading(dev.ctx, stepReading.features.data(), dim, stepReading.n, I.data()));

@@ -159,6 +159,38 @@ struct PointMatcher {
             pmx_quality q{};
         };
         mutable Quality quality_;
+        // getErrorElements (PointMatcher.h:549-551, ErrorMinimizer.cpp:58-193):
+        // the pairs the last minimiser call kept.  Empty before any compute
+        // (the reference's default-constructed lastErrorElements).  Once a
+        // checker has stopped the ICP the first call compacts the resident
+        // match on the device (pmx_error_elements_prepare, or the loop's form,
+        // by the path that ran), fetches the columns and gathers the
+        // descriptors of the filtered host clouds by reading index / reference
+        // id; cached until the next prepare / setMap.  The reading's "normals"
+        // and "observationDirections" are rotated as the reference's
+        // transformations leave them (T_refMean_dataIn, then the match's
+        // T_iter; TransformationsImpl.cpp:72-84), each component
+        // (m0 n0 + m1 n1) + m2 n2 in T.  A multi-rank ICP returns its shard.
+        struct ErrorElements {
+            DataPoints reading, reference;       // P columns each, every descriptor of the filtered clouds
+            std::vector<T> dists, weights;       // matches.dists / weights (1 x P)
+            std::vector<int32_t> ids;            // matches.ids (1 x P)
+            std::vector<int32_t> readingIndex;   // the column's point in the filtered reading
+            int64_t nbRejectedMatches = 0, nbRejectedPoints = 0;
+        };
+        const ErrorElements& getErrorElements() const;
+        struct Elements {
+            Device* dev = nullptr;
+            bool stopped = false, loop = false, valid = false;
+            // the filtered clouds the ICP had at prepare (shared, not copied);
+            // with readingStepDataPointsFilters the last iteration's step reading
+            std::shared_ptr<const DataPoints> reading, reference;
+            TransformationParameters T_pre;  // T_refMean_dataIn
+            bool normalsPre = false;         // the reading's "normals" already carry T_pre's rotation
+            int rows = 0;
+            ErrorElements e;
+        };
+        mutable Elements elements_;
         const pmx_quality& quality() const;  // throws the reference's runtime_error before any compute
         void setStats(const pmx_stats& st);
     };
@@ -247,7 +279,13 @@ struct PointMatcher {
 
         // the loop of computeWithTransformedReference (ICP.cpp:317-449) in three
         // phases, so a caller can time the iterations alone
+        // The clouds are read in place.  getErrorElements gathers their
+        // descriptors later: the shared form keeps them alive; the reference
+        // form expects the caller's clouds to live until it has been asked for
+        // (or never asks).
         void prepare(const DataPoints& reading, const DataPoints& reference, const TransformationParameters& T_init);
+        void prepare(std::shared_ptr<const DataPoints> reading, std::shared_ptr<const DataPoints> reference,
+                     const TransformationParameters& T_init);
         bool step();                          // one iteration; false when a checker stopped
         // up to n iterations; false when a checker stopped.  When every module
         // has a device form (loopConfig) the iterations run as the
@@ -270,6 +308,7 @@ struct PointMatcher {
         TransformationParameters computeSequence(const DataPoints& reading, const TransformationParameters& T_init);
         // its first phase (then iterate / finish as after prepare); false without a map
         bool prepareSequence(const DataPoints& reading, const TransformationParameters& T_init);
+        bool prepareSequence(std::shared_ptr<const DataPoints> reading, const TransformationParameters& T_init);
         // the map's matcher again after a chain reload (ICPSequence::setDefault /
         // loadFromYaml, ICP.cpp:520-539)
         void reinitMap();
@@ -291,7 +330,10 @@ struct PointMatcher {
       private:
         bool stepModules();                   // ICP.cpp:371-430 through the module calls
         bool loopConfig(pmx_loop_cfg& cfg) const;
-        void prepareReading(const DataPoints& readingIn, const TransformationParameters& T_init);
+        void prepareReading(std::shared_ptr<const DataPoints> readingIn, const TransformationParameters& T_init);
+        // getErrorElements' sources (ErrorMinimizer::Elements): shared with the minimiser when the loop stops
+        std::shared_ptr<const DataPoints> elemReading_, elemReference_;
+        bool elemStep_ = false, elemNormalsPre_ = false;
         // the reading's "normals" to the device when a filter of the chain
         // reads them (after every reading upload)
         void uploadReadingNormals(const DataPoints& reading);

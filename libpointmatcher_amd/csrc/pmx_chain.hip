@@ -580,7 +580,7 @@ int set_reference_impl(pmx_ctx* c, const T* feat, int rows, int64_t M, const T* 
     c->dim = D;
     c->M = M;
     c->M_pad = M_pad;
-    c->have_match = false;
+    c->have_match = c->elem_valid = false;
     c->grid_ready = false;
     // a resident reading keeps its slot order (any permutation is correct;
     // it was only chosen for the previous grid's locality)
@@ -686,7 +686,7 @@ int set_reading_impl(pmx_ctx* c, const T* feat, int rows, int64_t N, const T* T0
         c->N_total = (int64_t)hv[0];
         c->N_max = (int64_t)hv[1];
     }
-    c->have_match = false;
+    c->have_match = c->elem_valid = false;
     return PMX_OK;
 }
 
@@ -933,7 +933,7 @@ int match_impl(pmx_ctx* c, const T* Titer, int knn, double maxDist, uint64_t* vi
     c->knn = knn;
     c->have_match = true;
     c->chain_n = 0;  // new matches: the outlier chain starts over
-    c->w_valid = false;
+    c->w_valid = c->elem_valid = false;
     if (visited) *visited = c->visited_host;
     return PMX_OK;
 }
@@ -1123,7 +1123,7 @@ void chain_set(pmx_ctx* c, int pos, int type, double thr) {
     c->chain_n = pos + 1;
     c->chain_type[pos] = type;
     c->chain_thr[pos] = thr;
-    c->w_valid = false;
+    c->w_valid = c->elem_valid = false;
 }
 
 template <typename T>
@@ -1398,7 +1398,7 @@ int outlier_generic_impl(pmx_ctx* c, int pos, int soft, int larger_than, double 
 // built grid level's copy of it in position order
 template <typename T>
 int set_reference_wdesc_impl(pmx_ctx* c, const T* desc) {
-    c->w_valid = false;
+    c->w_valid = c->elem_valid = false;
     if (!desc) {
         if (c->has_wdesc && c->grid_ready) {
             c->has_wdesc = false;
@@ -1443,6 +1443,7 @@ int set_radii_impl(pmx_ctx* c, const T* radii) {
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's buffer may go)
     c->has_radii = true;
     c->safe_valid = false;  // (the previous match used other radii)
+    c->elem_valid = false;
     return PMX_OK;
 }
 
@@ -1451,7 +1452,7 @@ int set_radii_impl(pmx_ctx* c, const T* radii) {
 // block (what transformations.apply leaves in the reading, ICP.cpp:345-347)
 template <typename T>
 int set_reading_normals_impl(pmx_ctx* c, const T* normals) {
-    c->w_valid = false;
+    c->w_valid = c->elem_valid = false;
     if (!normals) {
         c->has_rnrm = false;
         return PMX_OK;
@@ -1856,6 +1857,137 @@ int quality_impl(pmx_ctx* c, const T* Tm_host, int minimizer, pmx_quality* out) 
     return PMX_OK;
 }
 
+// ErrorMinimizer::getErrorElements for the resident match, its chain record
+// and step transform (pmx_elements.h): flags, scan and compaction into the
+// context's buffer.  Never inside a loop; no collective (a rank's shard).
+namespace {
+// the columns' places in pmx_ctx::d_elem for P columns (every array on a 256-byte boundary)
+struct ElementsLayout {
+    size_t reading, reference, normals, dists, weights, ids, ridx, rank, bytes;
+};
+ElementsLayout elements_layout(size_t tsz, int rows, int64_t P) {
+    const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t p = (size_t)P;
+    ElementsLayout L{};
+    size_t at = 0;
+    L.reading = at, at += up(tsz * rows * p);
+    L.reference = at, at += up(tsz * rows * p);
+    L.normals = at, at += up(tsz * (rows - 1) * p);
+    L.dists = at, at += up(tsz * p);
+    L.weights = at, at += up(tsz * p);
+    L.ids = at, at += up(sizeof(int32_t) * p);
+    L.ridx = at, at += up(sizeof(int32_t) * p);
+    L.rank = at, at += up(sizeof(int32_t) * p);
+    L.bytes = at;
+    return L;
+}
+}  // namespace
+
+template <typename T>
+int elements_prepare_impl(pmx_ctx* c, const T* Tm_host, pmx_elements_info* info) {
+    std::memset(info, 0, sizeof(*info));
+    c->elem_valid = false;
+    int rc = check_match(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t N = c->N, n = c->N * c->knn;
+    if (n > (int64_t)INT32_MAX)
+        return fail(c, PMX_E_BAD_PARAM, "pmx_error_elements_prepare: more than 2^31 match entries");
+    if ((rc = materialise_weights<T>(c))) return rc;
+    // one context buffer: the inverse map, the two rejected counters, then the
+    // compaction's ballots, block counts and their scan (KeepScratch's layout)
+    const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t inv_b = up(sizeof(int32_t) * (size_t)std::max<int64_t>(N, 1)), cnt_b = 256;
+    const int64_t nb = (n + kKeepBlock - 1) / kKeepBlock;
+    const size_t mask_b = up(sizeof(unsigned long long) * (size_t)nb * kKeepWaves);
+    const size_t bc_b = up(sizeof(uint32_t) * (size_t)nb), off_b = up(sizeof(uint32_t) * (size_t)(nb + 1));
+    if ((rc = ensure(c, &c->d_elem_inv, &c->elem_inv_bytes, inv_b + cnt_b + mask_b + bc_b + off_b))) return rc;
+    char* const eb = (char*)c->d_elem_inv;
+    unsigned long long* counters = (unsigned long long*)(eb + inv_b);
+    HIPCHK(c, hipMemsetAsync(counters, 0, sizeof(unsigned long long) * kElCounters, c->stream));
+    ElementsIn<T> in{match_view<T>(c), (const T*)c->d_w, nullptr, c->ids_grid ? c->grid_valid : c->M};
+    if (c->has_order) {
+        launch_elements_inverse(c->d_order, N, (int32_t*)c->d_elem_inv, counters, c->stream);
+        in.inv = (const int32_t*)c->d_elem_inv;
+    }
+    unsigned long long hc[kElCounters] = {0, 0, 0};
+    uint32_t P = 0;
+    int ierr = 0;
+    // (a view of the context's buffer: nothing for KeepScratch's destructor to free)
+    struct ScratchView {
+        KeepScratch s;
+        ~ScratchView() { s.masks = nullptr; }
+    } view;
+    KeepScratch& sc = view.s;
+    sc.masks = (unsigned long long*)(eb + inv_b + cnt_b);
+    sc.cnt = (uint32_t*)(eb + inv_b + cnt_b + mask_b);
+    sc.off = (uint32_t*)(eb + inv_b + cnt_b + mask_b + bc_b);
+    sc.nb = nb;
+    if (n > 0) {
+        launch_elements_flag<T>(in, sc, counters, c->stream);
+        launch_keep_scan(sc, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&P, sc.off + sc.nb, sizeof(P), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(&ierr, c->d_iter_err, sizeof(ierr), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ierr == PMX_E_EMPTY_QUANTILE) return fail(c, PMX_E_EMPTY_QUANTILE, "no outlier to filter");
+    if (ierr && ierr != kSelTimeout) return fail(c, ierr, "quantile must be between 0 and 1");
+    if (hc[kElBadOrder])
+        return fail(c, PMX_E_STATE, "pmx_error_elements_prepare: the reading's slot order is not a permutation");
+    info->columns = (int64_t)P;
+    info->rejected_matches = (int64_t)hc[kElRejMatches];
+    info->rejected_points = (int64_t)hc[kElRejPoints];
+    if (P == 0) return fail(c, PMX_E_NO_POINTS, "ErrorMnimizer: no point to minimize");
+    const ElementsLayout L = elements_layout(sizeof(T), c->rows, (int64_t)P);
+    if ((rc = ensure(c, &c->d_elem, &c->elem_bytes, L.bytes))) return rc;
+    char* b = (char*)c->d_elem;
+    const ElementsOut<T> out{(T*)(b + L.reading), (T*)(b + L.reference),
+                             c->has_normals ? (T*)(b + L.normals) : nullptr, (T*)(b + L.dists),
+                             (int32_t*)(b + L.ids), (T*)(b + L.weights), (int32_t*)(b + L.ridx),
+                             (int32_t*)(b + L.rank)};
+    const Mat4<T> Tm = Tm_host ? embed<T>(Tm_host, c->rows) : step_mat<T>(c);
+    launch_elements_scatter<T>(in, Tm, c->rows, sc, out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->elem_P = (int64_t)P;
+    c->elem_valid = true;
+    return PMX_OK;
+}
+
+template <typename T>
+int elements_fetch_impl(pmx_ctx* c, void* reading, void* reference, void* ref_normals, void* dists, int32_t* ids,
+                        void* weights, int32_t* reading_index, int32_t* link_rank) {
+    int rc = check_match(c);
+    if (rc) return rc;
+    if (!c->elem_valid)
+        return fail(c, PMX_E_STATE,
+                    "pmx_error_elements: no prepared columns (pmx_error_elements_prepare first; a new match, chain, "
+                    "reading or reference drops them)");
+    if (ref_normals && !c->has_normals)
+        return fail(c, PMX_E_BAD_PARAM, "pmx_error_elements: the reference has no \"normals\"");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)c->elem_P, tsz = sizeof(T);
+    const ElementsLayout L = elements_layout(tsz, c->rows, c->elem_P);
+    const char* b = (const char*)c->d_elem;
+    const struct {
+        void* dst;
+        size_t at, bytes;
+    } copies[] = {{reading, L.reading, tsz * c->rows * P},
+                  {reference, L.reference, tsz * c->rows * P},
+                  {ref_normals, L.normals, tsz * (c->rows - 1) * P},
+                  {dists, L.dists, tsz * P},
+                  {weights, L.weights, tsz * P},
+                  {ids, L.ids, sizeof(int32_t) * P},
+                  {reading_index, L.ridx, sizeof(int32_t) * P},
+                  {link_rank, L.rank, sizeof(int32_t) * P}};
+    for (const auto& cp : copies)
+        if (cp.dst) HIPCHK(c, hipMemcpyAsync(cp.dst, b + cp.at, cp.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMX_OK;
+}
+
 template <typename T>
 int get_matches_impl(pmx_ctx* c, void* dists, int32_t* ids) {
     int rc = check_match(c);
@@ -1914,6 +2046,7 @@ int get_weights_impl(pmx_ctx* c, void* w) {
     template int p2point_enqueue<T>(pmx_ctx*, bool, PendingSums*);                          \
     template int p2plane_cov_impl<T>(pmx_ctx*, const T*, double*, double*, int64_t*);       \
     template int quality_impl<T>(pmx_ctx*, const T*, int, pmx_quality*);                    \
+    template int elements_prepare_impl<T>(pmx_ctx*, const T*, pmx_elements_info*);          \
     template int get_matches_impl<T>(pmx_ctx*, void*, int32_t*);                            \
     template int unpermute<T>(pmx_ctx*, const std::vector<T>&, T*, int);
 PMX_INST(float)
@@ -2037,6 +2170,39 @@ int pmx_match_quality(pmx_ctx* c, const void* T_step, int minimizer, pmx_quality
     if (!c || !out) return fail(c, PMX_E_BAD_PARAM, "null argument");
     return DISPATCH(c, quality_impl<float>(c, (const float*)T_step, minimizer, out),
                     quality_impl<double>(c, (const double*)T_step, minimizer, out));
+}
+
+int pmx_get_step_transform(pmx_ctx* c, void* T_step) {
+    if (!c || !T_step) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    const int rc = check_match(c);
+    if (rc) return rc;
+    // (Tstep is the embedded 4 x 4: a 2-D context's rows and columns are 0, 1, 3)
+    const int R = c->rows, at[4] = {0, 1, R == 4 ? 2 : 3, 3};
+    for (int i = 0; i < R; ++i)
+        for (int j = 0; j < R; ++j) {
+            const double v = c->Tstep[at[i] * 4 + at[j]];
+            if (c->dtype == PMX_F64)
+                ((double*)T_step)[i * R + j] = v;
+            else
+                ((float*)T_step)[i * R + j] = (float)v;
+        }
+    return PMX_OK;
+}
+
+int pmx_error_elements_prepare(pmx_ctx* c, const void* T_step, pmx_elements_info* info) {
+    if (!c || !info) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    return DISPATCH(c, elements_prepare_impl<float>(c, (const float*)T_step, info),
+                    elements_prepare_impl<double>(c, (const double*)T_step, info));
+}
+
+int pmx_error_elements(pmx_ctx* c, void* reading, void* reference, void* ref_normals, void* dists, int32_t* ids,
+                       void* weights, int32_t* reading_index, int32_t* link_rank) {
+    if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    return DISPATCH(c,
+                    elements_fetch_impl<float>(c, reading, reference, ref_normals, dists, ids, weights, reading_index,
+                                               link_rank),
+                    elements_fetch_impl<double>(c, reading, reference, ref_normals, dists, ids, weights, reading_index,
+                                                link_rank));
 }
 
 int pmx_p2point_system(pmx_ctx* c, double* mp, double* mq, double* m, pmx_stats* st) {

@@ -14,6 +14,7 @@
 #include "pmx_p2plane.h"
 #include "pmx_cov.h"
 #include "pmx_quality.h"
+#include "pmx_elements.h"
 #include "pmx_spec.h"
 
 #include <rccl/rccl.h>
@@ -243,6 +244,16 @@ struct pmx_ctx {
     int chain_type[kMaxChain] = {};
     double chain_thr[kMaxChain] = {};
     bool w_valid = false;  // d_w holds the chain's weights (mirror only)
+    // getErrorElements (pmx_elements.h): the columns pmx_error_elements_prepare
+    // left, one allocation (elements_layout, pmx_chain.hip) kept until the
+    // next prepare reuses it or the context goes; elem_valid falls with
+    // anything that changes the match, the chain or a cloud
+    void* d_elem = nullptr;
+    size_t elem_bytes = 0;
+    int64_t elem_P = 0;
+    bool elem_valid = false;
+    void* d_elem_inv = nullptr;  // reading index -> slot, int32[N], the counters, then the compaction's scratch
+    size_t elem_inv_bytes = 0;
     int limit_pos = 0;     // chain position whose quantile the last readback reports (readback)
     // RobustOutlierFilter (at most one per chain): its parameters, and the
     // device block of its scale state: SelectState (the MAD's second
@@ -465,6 +476,12 @@ int p2plane_cov_impl(pmx_ctx* c, const T* Tinc, double* H, double* Q, int64_t* p
 // pmx_match_quality on the resident match; Tm (rows x rows row-major T; null: the match's own) the step transform
 template <typename T>
 int quality_impl(pmx_ctx* c, const T* Tm, int minimizer, pmx_quality* out);
+// pmx_error_elements_prepare / pmx_error_elements on the resident match (pmx_elements.h); Tm as quality_impl's
+template <typename T>
+int elements_prepare_impl(pmx_ctx* c, const T* Tm, pmx_elements_info* info);
+template <typename T>
+int elements_fetch_impl(pmx_ctx* c, void* reading, void* reference, void* ref_normals, void* dists, int32_t* ids,
+                        void* weights, int32_t* reading_index, int32_t* link_rank);
 template <typename T>
 int get_matches_impl(pmx_ctx* c, void* dists, int32_t* ids);
 template <typename V>

@@ -346,6 +346,9 @@ __device__ __forceinline__ void keep_block_ballot(bool k, unsigned long long* __
         block_cnt[blockIdx.x] = c;
     }
 }
+// the exclusive scan of s.cnt into s.off (s.off[s.nb] = the kept count), for a
+// caller that scatters by itself (pmx_elements.hip)
+void launch_keep_scan(const KeepScratch& s, hipStream_t st);
 template <typename T>
 int keep_compact(const T* d_f, int rows, const T* d_desc, int desc_dim, const KeepScratch& s, T* d_of,
                  T* d_od, int64_t* n_out, hipStream_t st);

@@ -393,6 +393,10 @@ int KeepScratch::alloc(int64_t n) {
     return PMX_OK;
 }
 
+void launch_keep_scan(const KeepScratch& s, hipStream_t st) {
+    hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(256), 0, st, s.cnt, s.nb, s.off);
+}
+
 // the scan and the scatter over the ballots and block counts a flag kernel left in s
 template <typename T>
 int keep_compact(const T* d_f, int rows, const T* d_desc, int desc_dim, const KeepScratch& s, T* d_of,

@@ -280,7 +280,7 @@ int loop_enqueue_iteration(pmx_ctx* c) {
         // at once); its quantile from the radix passes, then the rest
         c->spec_exchanged = true;
         c->chain_n = 0;
-        c->w_valid = false;
+        c->w_valid = c->elem_valid = false;
     } else {
         if (c->shard_async) ++c->n_async;
         rc = match_impl<T>(c, Ir, cfg.knn, cfg.max_dist, nullptr);
@@ -545,6 +545,16 @@ int loop_quality_impl(pmx_ctx* c, int minimizer, pmx_quality* out) {
     return quality_impl<T>(c, nullptr, minimizer, out);
 }
 
+// pmx_loop_error_elements_prepare: the same resident state, as columns
+template <typename T>
+int loop_elements_impl(pmx_ctx* c, pmx_elements_info* info) {
+    if (!c->loop_begun || !c->loop_done || c->loop_err)
+        return fail(c, PMX_E_STATE,
+                    "pmx_loop_error_elements_prepare: the device loop has not finished, or stopped on an error");
+    c->w_valid = false;  // (as pmx_loop_quality: the weights again at Tstep)
+    return elements_prepare_impl<T>(c, nullptr, info);
+}
+
 template <typename T>
 int loop_trace_impl(pmx_ctx* c, int first, int count, void* out) {
     if (!c->loop_begun || !c->loop_cfg.keep_trace) return fail(c, PMX_E_STATE, "no loop trace (keep_trace = 0)");
@@ -585,6 +595,12 @@ int pmx_loop_quality(pmx_ctx* c, int minimizer, pmx_quality* out) {
     if (!c || !out) return fail(c, PMX_E_BAD_PARAM, "null argument");
     (void)hipSetDevice(c->device);
     return DISPATCH(c, loop_quality_impl<float>(c, minimizer, out), loop_quality_impl<double>(c, minimizer, out));
+}
+
+int pmx_loop_error_elements_prepare(pmx_ctx* c, pmx_elements_info* info) {
+    if (!c || !info) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c, loop_elements_impl<float>(c, info), loop_elements_impl<double>(c, info));
 }
 
 int pmx_loop_trace(pmx_ctx* c, int first, int count, void* out) {

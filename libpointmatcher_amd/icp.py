@@ -102,6 +102,10 @@ def lib():
         l.pmx_icp_select_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         l.pmx_icp_comm_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 5
         l.pmx_icp_loop_diag.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        l.pmx_icp_error_elements_info.argtypes = [C.c_void_p, C.POINTER(IcpElementsInfo)]
+        l.pmx_icp_error_elements.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+        l.pmx_icp_error_elements_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_int64,
+                                                        C.POINTER(C.c_int)]
         l.pmx_icp_set_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.POINTER(C.c_int)]
         l.pmx_icp_clear_map.argtypes = [C.c_void_p]
         l.pmx_icp_has_map.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
@@ -111,6 +115,29 @@ def lib():
         l.pmx_icp_sequence_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
+
+
+class IcpElementsInfo(C.Structure):
+    """pmx_icp_elements_info (include/pmx_icp.h)."""
+    _fields_ = [("columns", C.c_int64), ("rows", C.c_int), ("reading_desc_dim", C.c_int),
+                ("reference_desc_dim", C.c_int), ("rejected_matches", C.c_int64), ("rejected_points", C.c_int64)]
+
+
+class IcpErrorElements:
+    """errorMinimizer->getErrorElements() as numpy arrays: reading / reference
+    (P, rows) features, dists, weights (P,), ids, reading_index (P,) int32, the two
+    rejected counts, and descriptor(cloud, name) -> (P, span) or None."""
+
+    def __init__(self, icp, **kw):
+        self._icp = icp
+        self.__dict__.update(kw)
+
+    @property
+    def columns(self):
+        return len(self.dists)
+
+    def descriptor(self, cloud, name):
+        return self._icp._elements_descriptor(cloud, name, self.columns)
 
 
 def outlier_filter_doc(name, dtype=np.float32):
@@ -316,6 +343,33 @@ class ICP:
         v = C.c_double()
         self._chk(self._l.pmx_icp_residual_error(self.h, C.byref(v)))
         return v.value
+
+    def error_elements(self):
+        """errorMinimizer->getErrorElements() of the last compute (pmx_icp_error_elements*):
+        the kept pairs, computed on the first call after the ICP stopped and cached
+        until the next prepare / set_map; zero columns before any compute."""
+        info = IcpElementsInfo()
+        self._chk(self._l.pmx_icp_error_elements_info(self.h, C.byref(info)))
+        P, r = info.columns, info.rows if info.rows else (self.rows or 4)
+        e = IcpErrorElements(self, reading=np.empty((P, r), self.dtype), reference=np.empty((P, r), self.dtype),
+                             dists=np.empty(P, self.dtype), ids=np.empty(P, np.int32),
+                             weights=np.empty(P, self.dtype), reading_index=np.empty(P, np.int32),
+                             rejected_matches=info.rejected_matches, rejected_points=info.rejected_points,
+                             reading_desc_dim=info.reading_desc_dim, reference_desc_dim=info.reference_desc_dim)
+        self._chk(self._l.pmx_icp_error_elements(self.h, P, _p(e.reading), _p(e.reference), _p(e.dists), _p(e.ids),
+                                                 _p(e.weights), _p(e.reading_index)))
+        return e
+
+    def _elements_descriptor(self, cloud, name, columns):
+        which = 0 if cloud == "reading" else 1
+        span = C.c_int(0)
+        self._chk(self._l.pmx_icp_error_elements_descriptor(self.h, which, name.encode(), None, 0, C.byref(span)))
+        if span.value == 0:
+            return None
+        out = np.empty((columns, span.value), self.dtype)
+        self._chk(self._l.pmx_icp_error_elements_descriptor(self.h, which, name.encode(), _p(out), out.size,
+                                                            C.byref(span)))
+        return out
 
     def filtered_descriptor(self, cloud, points, name):
         """The descriptor `name` of `points` after the chain's reading
