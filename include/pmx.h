@@ -52,6 +52,8 @@
  *   pmx_loop_error_elements_prepare
  *                       ErrorMinimizer::getErrorElements (PointMatcher.h:549-551,
  *                         ErrorMinimizer.cpp:58-193): the kept pairs themselves
+ *   pmx_transform_cloud Transformation::compute on a cloud the caller keeps
+ *                         (TransformationsImpl.cpp:49-231), stand-alone
  *   pmx_get_matches /   lazy host mirrors of Matches / OutlierWeights for
  *   pmx_get_weights       CPU modules and inspectors (PointMatcher.h:371-391)
  *
@@ -885,6 +887,38 @@ int pmx_sphericality(int device, int dtype, const void* eig_values, int64_t n, u
 int pmx_remove_sensor_bias(int device, int dtype, const void* feat, int rows, int64_t n, const void* desc,
                            int desc_dim, int inc_row, int obs_row, int sensor_type, double angle_threshold,
                            void* feat_out, void* desc_out, int64_t* n_out);
+
+/* ----------------------------------------------------- transformations --- */
+/* Transformation::compute (PointMatcher.h Transformation; TransformationsImpl.cpp:
+ * 49-87 RigidTransformation, :157-195 SimilarityTransformation, :215-231
+ * PureTranslation) on a whole cloud: feat_out = params * feat, and R * d for
+ * every listed descriptor span, R the top-left D x D block of params (D = rows
+ * - 1).  It checks nothing of params: checkParameters is the caller's (the host
+ * chain's Transformation classes, include/pmx_icp.h).
+ *   feat        rows x n point-major T, rows 3 or 4
+ *   params      rows x rows row-major T, as pmx_match's T_iter
+ *   desc        desc_dim x n point-major T, or NULL with desc_dim 0
+ *   span_rows   n_spans row offsets into desc, each naming D rows to rotate
+ *               ("normals", "observationDirections"); at most
+ *               PMX_TRANSFORM_MAX_SPANS, inside desc, not overlapping
+ *   feat_out    rows x n; desc_out desc_dim x n (NULL with desc_dim 0).  An
+ *               output may be its own input (identical or disjoint arrays).
+ *   kernel_ms   (may be NULL) the kernel's own time from HIP events on the
+ *               call's stream, without the copies
+ * Every feature row r, the homogeneous one included, is ((P_r0 x + P_r1 y) +
+ * P_r2 z) + P_r3 h, in 2-D (P_r0 x + P_r1 y) + P_r2 h; every span row the same
+ * sequential sum over R's row; every multiply and add in T and rounded on its
+ * own.  NaN and infinities go through the expression like any other value.
+ * Descriptor rows outside the spans come out bit-identical: they are copied on
+ * the host and never cross the bus.  n = 0 is a result.  PMX_E_BAD_PARAM for
+ * rows other than 3 or 4, a span that leaves desc or overlaps another, spans
+ * given without desc (desc_dim 0), more than PMX_TRANSFORM_MAX_SPANS spans;
+ * the checks hold for an empty cloud too.  Standalone like pmx_voxel_grid;
+ * pmx_last_error(NULL) on failure. */
+enum { PMX_TRANSFORM_MAX_SPANS = 8 };
+int pmx_transform_cloud(int device, int dtype, const void* feat, int rows, int64_t n, const void* params,
+                        const void* desc, int desc_dim, const int* span_rows, int n_spans, void* feat_out,
+                        void* desc_out, double* kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -223,6 +223,52 @@ int pmx_icp_sequence_prepare(pmx_icp* icp, const void* reading, int rows, int64_
 int pmx_icp_sequence_compute(pmx_icp* icp, const void* reading, int rows, int64_t N, const void* T_init,
                              void* T_out);
 
+/* Transformation (PointMatcher.h; Transformation.cpp:60-79, TransformationsImpl.cpp:
+ * 49-272): what the reference's applications call on the cloud once the ICP has
+ * returned its parameters (transformation->compute(cloud, T)).  Registered
+ * names: "RigidTransformation", "SimilarityTransformation", "PureTranslation";
+ * any other is PMX_ICP_INVALID_ELEMENT.  A failed create leaves its message in
+ * pmx_transformation_last_error(NULL) (per thread); every other call in the
+ * handle's.  The ICP loop does not use these objects: its transform stays fused
+ * into the match.
+ *   check_parameters    *ok = checkParameters(params), params rows x rows
+ *                       row-major T.  Rigid: |1 - det R| <= 0.001 in T;
+ *                       Similarity: always 1; PureTranslation: the matrix with
+ *                       its translation column zeroed isApprox(Identity)
+ *                       (Eigen's rule: ||A - I||_F^2 <= p^2 min(||A||_F^2,
+ *                       ||I||_F^2), p 1e-5 float / 1e-12 double).
+ *   correct_parameters  out = correctParameters(params) (rows x rows).  Rigid
+ *                       3-D: columns 1 and 2 normalised, c0 = c1 x c2, c1 = c2 x
+ *                       c0; 2-D: a = (p00 + p11) / 2, b = (-p10 + p01) / 2, both
+ *                       divided by sqrt(a a + b b), PMX_ICP_TRANSFORMATION_ERROR
+ *                       when |p00 - p11| or |p10 + p01| exceeds 0.001 (a
+ *                       reflection).  Similarity: params.  PureTranslation: the
+ *                       left block the identity, the bottom row 0 .. 0 1.
+ *                       Both are host arithmetic in T and need no GPU.
+ *   compute             feat_out = params * feat on the device
+ *                       (pmx_transform_cloud, include/pmx.h), and for Rigid and
+ *                       Similarity the rotation block times every descriptor
+ *                       labelled "normals" or "observationDirections"; every
+ *                       other descriptor row, and with PureTranslation all of
+ *                       them, bit-identical.  The descriptors come as
+ *                       pmx_cloud_data returns them (desc_dim x n point-major)
+ *                       with their labels as pmx_cloud_label lists them (names
+ *                       and spans, the spans summing to desc_dim).  An output
+ *                       may be its own input.  PMX_ICP_TRANSFORMATION_ERROR when
+ *                       check_parameters refuses params (nothing is written),
+ *                       PMX_ICP_INVALID_PARAMETER when params_rows != rows,
+ *                       PMX_ICP_INVALID_FIELD for a rotated label whose span is
+ *                       not rows - 1, PMX_ICP_RUNTIME_ERROR without a GPU. */
+typedef struct pmx_transformation pmx_transformation;
+int pmx_transformation_create(const char* name, int dtype, int device, pmx_transformation** out);
+void pmx_transformation_destroy(pmx_transformation* t);
+const char* pmx_transformation_last_error(const pmx_transformation* t);
+int pmx_transformation_check_parameters(pmx_transformation* t, const void* params, int rows, int* ok);
+int pmx_transformation_correct_parameters(pmx_transformation* t, const void* params, int rows, void* out);
+int pmx_transformation_compute(pmx_transformation* t, const void* feat, int rows, int64_t n, const void* params,
+                               int params_rows, const void* desc, int desc_dim, const char* const* label_names,
+                               const int* label_spans, int n_labels, void* feat_out, void* desc_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,7 +193,7 @@ EXPORTS = [
     "pmx_loop_begin", "pmx_loop_run", "pmx_loop_trace", "pmx_loop_select_stats", "pmx_loop_diag", "pmx_surface_normals",
     "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter", "pmx_octree_grid",
     "pmx_normal_space", "pmx_covariance_sampling",
-    "pmx_incidence_angles", "pmx_sphericality", "pmx_remove_sensor_bias",
+    "pmx_incidence_angles", "pmx_sphericality", "pmx_remove_sensor_bias", "pmx_transform_cloud",
 ]
 
 
@@ -288,6 +288,9 @@ def lib():
         l.pmx_remove_sensor_bias.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                              C.POINTER(C.c_int64)]
+        l.pmx_transform_cloud.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_double)]
         l.pmx_sampling_surface_normals.argtypes = ([C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint]
                                                    + [C.c_void_p] * 6 + [C.POINTER(C.c_int64)] * 2)
@@ -393,6 +396,45 @@ def voxel_grid(points, descriptors=None, vsize=(1.0, 1.0, 1.0), use_centroid=Tru
     if rc != PMX_OK:
         raise_for(rc, l.pmx_last_error(None).decode())
     return of[:no.value], od[:no.value]
+
+
+TRANSFORM_MAX_SPANS = 8  # PMX_TRANSFORM_MAX_SPANS
+
+
+def transform_cloud(points, params, descriptors=None, spans=(), device=0, in_place=False, timing=False):
+    """Transformation::compute on the GPU (pmx_transform_cloud): params * points,
+    and the rotation block of params times every descriptor span listed in
+    spans (row offsets, D = rows - 1 rows each).  points (n, rows) with the
+    homogeneous row last, params (rows, rows), descriptors (n, desc_dim) or
+    None.  Returns (features, descriptors or None), with timing=True also the
+    kernel's own milliseconds.  in_place: the outputs are the (contiguous,
+    float32 / float64) input arrays themselves.  It checks nothing of params:
+    icp.Transformation does."""
+    pts = np.ascontiguousarray(points)
+    if pts.dtype not in (np.float32, np.float64):
+        pts = pts.astype(np.float32)
+    dt = pts.dtype
+    n, rows = pts.shape
+    P = np.ascontiguousarray(params, dtype=dt)
+    if P.shape != (rows, rows):
+        raise InvalidParameter(f"params must be ({rows}, {rows}), not {P.shape}")
+    desc = None if descriptors is None else np.ascontiguousarray(descriptors, dtype=dt)
+    dd = 0 if desc is None else desc.shape[1]
+    if in_place:
+        if pts is not points or (desc is not None and desc is not descriptors):
+            raise InvalidParameter("in_place needs contiguous float32 / float64 arrays of one dtype")
+        of, od = pts, desc
+    else:
+        of = np.empty((n, rows), dt)
+        od = None if desc is None else np.empty((n, dd), dt)
+    sp = (C.c_int * max(len(spans), 1))(*[int(s) for s in spans])
+    ms = C.c_double(0.0)
+    l = lib()
+    rc = l.pmx_transform_cloud(int(device), PMX_F64 if dt == np.float64 else PMX_F32, _ptr(pts), rows, n, _ptr(P),
+                               _ptr(desc), dd, sp, len(spans), _ptr(of), _ptr(od), C.byref(ms) if timing else None)
+    if rc != PMX_OK:
+        raise_for(rc, l.pmx_last_error(None).decode())
+    return (of, od, ms.value) if timing else (of, od)
 
 
 KEEP_SHADOW, KEEP_MAX_QUANTILE, KEEP_REMOVE_NAN, KEEP_CUT_DESCRIPTOR = range(4)  # PMX_KEEP_*

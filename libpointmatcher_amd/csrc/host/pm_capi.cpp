@@ -701,3 +701,131 @@ int pmx_cloud_data(const pmx_cloud* c, void* feat, void* desc) {
 
 }  // extern "C"
 
+// ------------------------------------------------------- transformations --
+struct pmx_transformation {
+    int dtype = 0;
+    std::shared_ptr<pm::PointMatcher<float>::Transformation> f;
+    std::shared_ptr<pm::PointMatcher<double>::Transformation> d;
+    std::string err;
+};
+
+namespace {
+thread_local std::string g_transformation_err;  // a failed create has no handle to keep its message
+
+// the exception -> code mapping of guarded(), the message into `err`
+template <typename F>
+int guarded_to(std::string& err, F&& fn) {
+    pmx_icp tmp;
+    const int rc = guarded(&tmp, fn);
+    if (rc) err = tmp.err;
+    return rc;
+}
+
+template <typename T>
+void transformation_compute_impl(const typename pm::PointMatcher<T>::Transformation& t, const void* feat, int rows,
+                                 int64_t n, const void* params, int params_rows, const void* desc, int desc_dim,
+                                 const char* const* names, const int* spans, int n_labels, void* feat_out,
+                                 void* desc_out) {
+    if (rows < 1 || n < 0 || desc_dim < 0 || n_labels < 0 || params_rows < 0 || !params ||
+        (n > 0 && (!feat || !feat_out)) || (desc_dim > 0 && n > 0 && (!desc || !desc_out)) ||
+        (n_labels > 0 && (!names || !spans)))
+        throw InvalidParameter("pmx_transformation_compute: null or negative argument");
+    if (rows != 3 && rows != 4)
+        throw InvalidParameter("pmx_transformation_compute: clouds must be 2-D or 3-D (3 or 4 homogeneous rows)");
+    DataPoints<T> in = make_cloud<T>(feat, rows, n, nullptr);
+    int sum = 0;
+    for (int i = 0; i < n_labels; ++i) {
+        if (!names[i] || spans[i] < 1) throw InvalidParameter("pmx_transformation_compute: bad descriptor label");
+        in.descriptorLabels.push_back({names[i], spans[i]});
+        sum += spans[i];
+    }
+    if (sum != desc_dim)
+        throw InvalidParameter("pmx_transformation_compute: the labels span " + std::to_string(sum) +
+                               " rows, the descriptors have " + std::to_string(desc_dim));
+    in.descDim = desc_dim;
+    in.extDesc = static_cast<const T*>(desc);
+    const T* p = static_cast<const T*>(params);
+    const std::vector<T> P(p, p + (size_t)params_rows * params_rows);
+    const DataPoints<T> out = t.compute(in, P);
+    if (n > 0) std::memcpy(feat_out, out.features.data(), sizeof(T) * out.features.size());
+    if (n > 0 && desc_dim > 0) std::memcpy(desc_out, out.descriptors.data(), sizeof(T) * out.descriptors.size());
+}
+}  // namespace
+
+extern "C" {
+
+int pmx_transformation_create(const char* name, int dtype, int device, pmx_transformation** out) {
+    if (!name || !out || (dtype != 0 && dtype != 1)) {
+        g_transformation_err = "null argument or bad dtype";
+        return PMX_ICP_INVALID_PARAMETER;
+    }
+    *out = nullptr;
+    auto t = std::make_unique<pmx_transformation>();
+    t->dtype = dtype;
+    const int rc = guarded_to(g_transformation_err, [&] {
+        if (dtype == 1) {
+            t->d = pm::PointMatcher<double>::get().TransformationRegistrar.create(name);
+            t->d->device = device;
+        } else {
+            t->f = pm::PointMatcher<float>::get().TransformationRegistrar.create(name);
+            t->f->device = device;
+        }
+    });
+    if (rc == PMX_ICP_OK) *out = t.release();
+    return rc;
+}
+
+void pmx_transformation_destroy(pmx_transformation* t) { delete t; }
+
+const char* pmx_transformation_last_error(const pmx_transformation* t) {
+    return t ? t->err.c_str() : g_transformation_err.c_str();
+}
+
+int pmx_transformation_check_parameters(pmx_transformation* t, const void* params, int rows, int* ok) {
+    if (!t) return PMX_ICP_INVALID_PARAMETER;
+    return guarded_to(t->err, [&] {
+        if (!params || !ok || rows < 0) throw InvalidParameter("pmx_transformation_check_parameters: null argument");
+        const size_t sz = (size_t)rows * rows;
+        if (t->dtype == 1) {
+            const double* p = static_cast<const double*>(params);
+            *ok = t->d->checkParameters(std::vector<double>(p, p + sz)) ? 1 : 0;
+        } else {
+            const float* p = static_cast<const float*>(params);
+            *ok = t->f->checkParameters(std::vector<float>(p, p + sz)) ? 1 : 0;
+        }
+    });
+}
+
+int pmx_transformation_correct_parameters(pmx_transformation* t, const void* params, int rows, void* out) {
+    if (!t) return PMX_ICP_INVALID_PARAMETER;
+    return guarded_to(t->err, [&] {
+        if (!params || !out || rows < 0) throw InvalidParameter("pmx_transformation_correct_parameters: null argument");
+        const size_t sz = (size_t)rows * rows;
+        if (t->dtype == 1) {
+            const double* p = static_cast<const double*>(params);
+            const auto r = t->d->correctParameters(std::vector<double>(p, p + sz));
+            std::memcpy(out, r.data(), sizeof(double) * sz);
+        } else {
+            const float* p = static_cast<const float*>(params);
+            const auto r = t->f->correctParameters(std::vector<float>(p, p + sz));
+            std::memcpy(out, r.data(), sizeof(float) * sz);
+        }
+    });
+}
+
+int pmx_transformation_compute(pmx_transformation* t, const void* feat, int rows, int64_t n, const void* params,
+                               int params_rows, const void* desc, int desc_dim, const char* const* label_names,
+                               const int* label_spans, int n_labels, void* feat_out, void* desc_out) {
+    if (!t) return PMX_ICP_INVALID_PARAMETER;
+    return guarded_to(t->err, [&] {
+        if (t->dtype == 1)
+            transformation_compute_impl<double>(*t->d, feat, rows, n, params, params_rows, desc, desc_dim, label_names,
+                                                label_spans, n_labels, feat_out, desc_out);
+        else
+            transformation_compute_impl<float>(*t->f, feat, rows, n, params, params_rows, desc, desc_dim, label_names,
+                                               label_spans, n_labels, feat_out, desc_out);
+    });
+}
+
+}  // extern "C"
+

@@ -2083,6 +2083,7 @@ PointMatcher<T>::PointMatcher() {
     LoggerRegistrar.reg("FileLogger", [](const Ps& p) {
         return std::make_shared<NoOp<Logger>>("FileLogger", filelogger_doc(), p);
     }, true);
+    registerTransformations();
 }
 
 template <typename T>

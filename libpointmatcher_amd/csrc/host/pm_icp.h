@@ -235,6 +235,26 @@ struct PointMatcher {
             for (auto& f : *this) f->inPlaceFilter(c);
         }
     };
+    // ---------------------------------------------------- Transformation --
+    // Transformation (PointMatcher.h, Transformation.cpp:60-79,
+    // TransformationsImpl.cpp:49-272): what a caller applies to a cloud once
+    // the ICP has returned its parameters.  compute runs on the GPU
+    // (pmx_transform_cloud); the two parameter functions are host arithmetic
+    // in T and need no device.  The ICP loop does not go through these
+    // classes: its transform stays fused into the match.
+    struct Transformation : Parametrizable {
+        Transformation() {}
+        Transformation(const std::string& n, const ParametersDoc& d, const Parameters& p) : Parametrizable(n, d, p) {}
+        virtual ~Transformation() {}
+        // the transformed copy of input.  InvalidParameter when parameters is
+        // not rows x rows; TransformationError when checkParameters refuses
+        // them; InvalidField for a rotated descriptor whose span is not D
+        virtual DataPoints compute(const DataPoints& input, const TransformationParameters& parameters) const = 0;
+        virtual bool checkParameters(const TransformationParameters& parameters) const = 0;
+        virtual TransformationParameters correctParameters(const TransformationParameters& parameters) const = 0;
+        int device = 0;  // HIP device compute runs on
+    };
+
     struct Inspector : Parametrizable {
         Inspector() {}
         Inspector(const std::string& n, const ParametersDoc& d, const Parameters& p) : Parametrizable(n, d, p) {}
@@ -254,6 +274,8 @@ struct PointMatcher {
     Registrar<DataPointsFilter> DataPointsFilterRegistrar;
     Registrar<Inspector> InspectorRegistrar;
     Registrar<Logger> LoggerRegistrar;
+    Registrar<Transformation> TransformationRegistrar;
+    void registerTransformations();  // pm_transformation.cpp (Registry.cpp:60-64)
     PointMatcher();
     static const PointMatcher& get();
 

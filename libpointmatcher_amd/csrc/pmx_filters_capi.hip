@@ -2,7 +2,8 @@
 // SurfaceNormal, SamplingSurfaceNormal, VoxelGrid, OctreeGrid, the keep-filters and the
 // sensor-bias family (IncidenceAngle, Sphericality, RemoveSensorBias) on the
 // device, each on a temporary context or stream (the self-match of the normals
-// uses the grid match).
+// uses the grid match); and pmx_transform_cloud, the Transformation modules'
+// compute, which is stand-alone in the same way.
 #include "pmx_ctx.h"
 #include "common/pmx_covs.h"
 #include "common/pmx_nss.h"
@@ -573,6 +574,110 @@ int sensor_bias_impl(int device, const T* feat, int rows, int64_t n, const T* de
     return PMX_OK;
 }
 
+// Transformation::compute (pmx_transform.hip): the checks before the device is
+// touched (they hold for an empty cloud too), then upload, one kernel in place
+// on the device, download.  Only the listed spans cross the bus: when other
+// descriptor rows exist the spans are packed on the host into records of
+// n_spans * D rows, rotated there and scattered back; the other rows are a host
+// copy.  Spans that tile the whole descriptor are uploaded as they are.
+template <typename T>
+int transform_impl(int device, const T* feat, int rows, int64_t n, const T* params, const T* desc, int desc_dim,
+                   const int* spans, int n_spans, T* feat_out, T* desc_out, double* kernel_ms) {
+    const char* who = "Transformation";
+    if (kernel_ms) *kernel_ms = 0;
+    if (rows != 3 && rows != 4) {
+        g_err = std::string(who) + ": clouds must be 2-D or 3-D (3 or 4 homogeneous rows)";
+        return PMX_E_BAD_PARAM;
+    }
+    if (n < 0 || desc_dim < 0 || n_spans < 0) {
+        g_err = std::string(who) + ": the point count, the descriptor dimension and the span count must be >= 0";
+        return PMX_E_BAD_PARAM;
+    }
+    if (n_spans > kXformMaxSpans) {
+        g_err = std::string(who) + ": more than " + std::to_string(kXformMaxSpans) + " spans to rotate";
+        return PMX_E_BAD_PARAM;
+    }
+    if (n_spans > 0 && (desc_dim == 0 || !spans || (!desc && n > 0))) {
+        g_err = std::string(who) + ": spans to rotate were given without descriptors";
+        return PMX_E_BAD_PARAM;
+    }
+    const int D = rows - 1;
+    for (int k = 0; k < n_spans; ++k) {
+        if (spans[k] < 0 || spans[k] > desc_dim - D) {
+            g_err = std::string(who) + ": span " + std::to_string(k) + " (rows " + std::to_string(spans[k]) + " .. " +
+                    std::to_string((int64_t)spans[k] + D - 1) + ") leaves the " + std::to_string(desc_dim) +
+                    " descriptor rows";
+            return PMX_E_BAD_PARAM;
+        }
+        for (int j = 0; j < k; ++j)
+            if (spans[j] < spans[k] + D && spans[k] < spans[j] + D) {
+                g_err = std::string(who) + ": spans " + std::to_string(j) + " and " + std::to_string(k) + " overlap";
+                return PMX_E_BAD_PARAM;
+            }
+    }
+    if ((n + 255) / 256 > (int64_t)0x7fffffff) {
+        g_err = std::string(who) + ": more than 2^39 points";
+        return PMX_E_BAD_PARAM;
+    }
+    if (n == 0) return PMX_OK;
+    XformArgs<T> a{};
+    for (int e = 0; e < rows * rows; ++e) a.p[e] = params[e];
+    a.nspan = n_spans;
+    const int S = n_spans * D;           // span rows per point
+    const bool packed = S < desc_dim;    // (no overlap: S == desc_dim means the spans tile the descriptor)
+    for (int k = 0; k < n_spans; ++k) a.off[k] = packed ? k * D : spans[k];
+    std::vector<T> pk;
+    if (packed && S > 0) {
+        pk.resize((size_t)S * (size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < n_spans; ++k)
+                for (int r = 0; r < D; ++r) pk[(size_t)(i * S + k * D + r)] = desc[i * desc_dim + spans[k] + r];
+    }
+    const T* h_sp = packed ? pk.data() : desc;  // what is uploaded when S > 0
+    const size_t fb = sizeof(T) * (size_t)rows * n, sb = sizeof(T) * (size_t)S * n, fa = pad256(fb);
+    FilterDevice dev;
+    int rc = dev.open(device, fa + sb, who);
+    if (rc) return rc;
+    T* d_f = (T*)dev.buf;
+    T* d_s = sb ? (T*)(dev.buf + fa) : nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events {
+        hipEvent_t &a, &b;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } events{ev0, ev1};
+    bool ok = hipMemcpyAsync(d_f, feat, fb, hipMemcpyHostToDevice, dev.st) == hipSuccess &&
+              (!sb || hipMemcpyAsync(d_s, h_sp, sb, hipMemcpyHostToDevice, dev.st) == hipSuccess);
+    if (ok && kernel_ms)
+        ok = hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess &&
+             hipEventRecord(ev0, dev.st) == hipSuccess;
+    if (ok) launch_transform_cloud<T>(d_f, rows, n, a, d_s, S, d_f, d_s, dev.st);
+    ok = ok && hipGetLastError() == hipSuccess;
+    if (ok && kernel_ms) ok = hipEventRecord(ev1, dev.st) == hipSuccess;
+    // the rows the transformation leaves alone (with the rotated spans' old
+    // values, overwritten below): a host copy while the device works
+    if (ok && packed && desc_out != desc) std::memcpy(desc_out, desc, sizeof(T) * (size_t)desc_dim * n);
+    T* h_so = packed ? pk.data() : desc_out;
+    ok = ok && hipMemcpyAsync(feat_out, d_f, fb, hipMemcpyDeviceToHost, dev.st) == hipSuccess &&
+         (!sb || hipMemcpyAsync(h_so, d_s, sb, hipMemcpyDeviceToHost, dev.st) == hipSuccess) &&
+         hipStreamSynchronize(dev.st) == hipSuccess;
+    if (!ok) {
+        g_err = std::string(who) + ": HIP failure";
+        return PMX_E_HIP;
+    }
+    if (kernel_ms) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *kernel_ms = ms;
+    }
+    if (packed && S > 0)
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < n_spans; ++k)
+                for (int r = 0; r < D; ++r) desc_out[i * desc_dim + spans[k] + r] = pk[(size_t)(i * S + k * D + r)];
+    return PMX_OK;
+}
+
 template <typename T>
 int ssn_impl(int device, const T* feat, int rows, int64_t n, const T* desc, int desc_dim, int knn, int method,
              double ratio_d, double max_box_d, unsigned flags, T* feat_out, T* desc_out, T* o_nrm, T* o_dens,
@@ -857,6 +962,23 @@ int pmx_remove_sensor_bias(int device, int dtype, const void* feat, int rows, in
         return sensor_bias_impl<double>(device, (const double*)feat, rows, n, (const double*)desc, desc_dim, inc_row,
                                         obs_row, sensor_type, angle_threshold, (double*)feat_out, (double*)desc_out,
                                         n_out);
+    g_err = "dtype must be PMX_F32 or PMX_F64";
+    return PMX_E_BAD_PARAM;
+}
+
+int pmx_transform_cloud(int device, int dtype, const void* feat, int rows, int64_t n, const void* params,
+                        const void* desc, int desc_dim, const int* span_rows, int n_spans, void* feat_out,
+                        void* desc_out, double* kernel_ms) {
+    if (!params || (n > 0 && (!feat || !feat_out || (desc_dim > 0 && (!desc || !desc_out))))) {
+        g_err = "null argument";
+        return PMX_E_BAD_PARAM;
+    }
+    if (dtype == PMX_F32)
+        return transform_impl<float>(device, (const float*)feat, rows, n, (const float*)params, (const float*)desc,
+                                     desc_dim, span_rows, n_spans, (float*)feat_out, (float*)desc_out, kernel_ms);
+    if (dtype == PMX_F64)
+        return transform_impl<double>(device, (const double*)feat, rows, n, (const double*)params, (const double*)desc,
+                                      desc_dim, span_rows, n_spans, (double*)feat_out, (double*)desc_out, kernel_ms);
     g_err = "dtype must be PMX_F32 or PMX_F64";
     return PMX_E_BAD_PARAM;
 }

@@ -393,6 +393,21 @@ template <typename T>
 int sensor_bias_run(const T* d_f, int rows, int64_t n, const T* d_desc, int desc_dim, int inc_row, int obs_row,
                     int sensor_type, double angle_threshold, T* d_cf, T* d_of, T* d_od, int64_t* n_out,
                     hipStream_t st, std::string& err);
+// Transformation::compute on a whole cloud (pmx_transform.hip; the parameters:
+// pmx_transform_cloud of include/pmx.h); device pointers, point-major.  a.p: the
+// rows x rows row-major parameters; a.off[0 .. a.nspan): row offsets, in a
+// descriptor record of `stride` rows, of the D-row spans the rotation block
+// multiplies.  An output may be its own input.
+constexpr int kXformMaxSpans = 8;  // (PMX_TRANSFORM_MAX_SPANS)
+template <typename T>
+struct XformArgs {
+    T p[16];
+    int nspan;
+    int off[kXformMaxSpans];
+};
+template <typename T>
+void launch_transform_cloud(const T* feat, int rows, int64_t n, const XformArgs<T>& a, const T* desc, int stride,
+                            T* feat_out, T* desc_out, hipStream_t st);
 // code-object preloads (one per translation unit, called by pmx_ctx_create)
 void preload_setup();
 void preload_ssn();

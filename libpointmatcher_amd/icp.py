@@ -3,6 +3,7 @@
     icp = ICP(np.float32)
     icp.load_yaml(open("chain.yaml").read())     # or icp.set_default()
     T = icp.compute(reading, reference, ref_normals)
+    aligned, _ = Transformation("RigidTransformation").compute(reading, T)
 
 Clouds are (n, rows) arrays with the homogeneous row last (rows = D + 1) —
 the memory layout of the reference's column-major (D+1) x n features.
@@ -113,6 +114,15 @@ def lib():
         l.pmx_icp_sequence_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                C.POINTER(C.c_int)]
         l.pmx_icp_sequence_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+        l.pmx_transformation_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        l.pmx_transformation_destroy.argtypes = [C.c_void_p]
+        l.pmx_transformation_last_error.argtypes = [C.c_void_p]
+        l.pmx_transformation_last_error.restype = C.c_char_p
+        l.pmx_transformation_check_parameters.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.pmx_transformation_correct_parameters.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        l.pmx_transformation_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
+                                                 C.c_int, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 
@@ -212,6 +222,97 @@ def load_cloud(path, dtype=np.float32):
         return Cloud(f, labels[0], d, labels[1])
     finally:
         l.pmx_cloud_destroy(h)
+
+
+class Transformation:
+    """A registered Transformation (PointMatcher.h; TransformationsImpl.cpp:49-272):
+    "RigidTransformation", "SimilarityTransformation" or "PureTranslation".
+
+        T = icp.compute(reading, reference, normals)
+        aligned = Transformation("RigidTransformation").compute(reading_cloud, T)
+
+    check_parameters and correct_parameters are host arithmetic and need no
+    GPU; compute runs on the GPU and raises without one."""
+
+    def __init__(self, name, dtype=np.float32, device=0):
+        self.dtype = np.dtype(dtype)
+        self.name = name
+        self._l = lib()
+        h = C.c_void_p()
+        rc = self._l.pmx_transformation_create(name.encode(), 1 if self.dtype == np.float64 else 0, int(device),
+                                               C.byref(h))
+        if rc:
+            raise _ERR.get(rc, RuntimeError)(self._l.pmx_transformation_last_error(None).decode())
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._l.pmx_transformation_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc:
+            raise _ERR.get(rc, RuntimeError)(self._l.pmx_transformation_last_error(self.h).decode())
+
+    def _params(self, T):
+        P = np.ascontiguousarray(T, dtype=self.dtype)
+        if P.ndim != 2 or P.shape[0] != P.shape[1]:
+            raise InvalidParameter(f"transformation parameters must be a square matrix, not {P.shape}")
+        return P
+
+    def check_parameters(self, T):
+        P = self._params(T)
+        ok = C.c_int(0)
+        self._chk(self._l.pmx_transformation_check_parameters(self.h, _p(P), P.shape[0], C.byref(ok)))
+        return bool(ok.value)
+
+    def correct_parameters(self, T):
+        P = self._params(T)
+        out = np.empty_like(P)
+        self._chk(self._l.pmx_transformation_correct_parameters(self.h, _p(P), P.shape[0], _p(out)))
+        return out
+
+    def compute(self, cloud_or_features, T, descriptors=None, descriptor_labels=None):
+        """The transformed copy of a Cloud (a Cloud is returned), or of a
+        features array (n, rows) with optional descriptors (n, desc_dim) and
+        their labels [(name, span)]: (features, descriptors or None) is
+        returned.  The inputs are left as they are."""
+        is_cloud = isinstance(cloud_or_features, Cloud)
+        if is_cloud:
+            if descriptors is not None or descriptor_labels is not None:
+                raise ValueError("a Cloud carries its own descriptors and labels")
+            cloud = cloud_or_features
+            feat, descriptors, descriptor_labels = cloud.features, cloud.descriptors, cloud.descriptor_labels
+            if descriptors is not None and descriptors.shape[1] == 0:
+                descriptors = None
+        else:
+            feat = cloud_or_features
+        f = np.ascontiguousarray(feat, dtype=self.dtype)
+        if f.ndim != 2:
+            raise InvalidParameter("features must be (n, rows)")
+        n, rows = f.shape
+        P = self._params(T)
+        d = None if descriptors is None else np.ascontiguousarray(descriptors, dtype=self.dtype)
+        if d is not None and (d.ndim != 2 or d.shape[0] != n):
+            raise InvalidParameter("descriptors must be (n, desc_dim)")
+        dd = 0 if d is None else d.shape[1]
+        labels = list(descriptor_labels or [])
+        names = (C.c_char_p * max(len(labels), 1))(*[str(name).encode() for name, _ in labels])
+        spans = (C.c_int * max(len(labels), 1))(*[int(span) for _, span in labels])
+        of = np.empty_like(f)
+        od = None if d is None else np.empty_like(d)
+        self._chk(self._l.pmx_transformation_compute(self.h, _p(f), rows, n, _p(P), P.shape[0], _p(d), dd, names,
+                                                     spans, len(labels), _p(of), _p(od)))
+        if is_cloud:
+            return Cloud(of, list(cloud.feature_labels), od if od is not None else np.empty((n, 0), self.dtype),
+                         list(cloud.descriptor_labels))
+        return of, od
 
 
 class ICP:
