@@ -54,6 +54,9 @@
  *                         ErrorMinimizer.cpp:58-193): the kept pairs themselves
  *   pmx_transform_cloud Transformation::compute on a cloud the caller keeps
  *                         (TransformationsImpl.cpp:49-231), stand-alone
+ *   pmx_transform_reading / pmx_transform_reading_offset
+ *                       the same on the context's resident reading: no upload,
+ *                         T_iter of a finished device loop read on the device
  *   pmx_get_matches /   lazy host mirrors of Matches / OutlierWeights for
  *   pmx_get_weights       CPU modules and inspectors (PointMatcher.h:371-391)
  *
@@ -569,6 +572,28 @@ int pmx_loop_quality(pmx_ctx* ctx, int minimizer, pmx_quality* out);
 /* pmx_error_elements_prepare for a finished loop: its last match and step
  * transform, as pmx_loop_quality; pmx_error_elements then copies the columns. */
 int pmx_loop_error_elements_prepare(pmx_ctx* ctx, pmx_elements_info* info);
+/* transformation->compute(reading, T) on the context's resident reading:
+ * feat_out rows x N point-major T in the caller's index order; normals_out
+ * D x N or NULL (PMX_E_STATE when asked for and no reading normals are set).
+ * T_params rows x rows row-major T; NULL: the finished loop's T_iter, read on
+ * the device (PMX_E_STATE without a finished loop, or after one that stopped
+ * on an error).  Synchronises the stream.
+ * The points are the reading as the context holds it, T0 * reading
+ * (pmx_set_reading) and the normals R0 * normals (pmx_set_reading_normals);
+ * nothing is uploaded, one kernel (pmx_transform.hip) and one download per
+ * output.  Every row is pmx_transform_cloud's separately rounded expression,
+ * the homogeneous one included; the normals get the rotation block only.
+ * "Finished loop" means a pmx_loop_begin after the last pmx_set_reading whose
+ * pmx_loop_run reported done.  PMX_E_STATE when no reading is set; N = 0 is a
+ * result.  Several ranks: each transforms its own shard, no collective. */
+int pmx_transform_reading(pmx_ctx* ctx, const void* T_params, void* feat_out, void* normals_out);
+/* The same with a translation added to each coordinate r < D after the
+ * expression, (...) + offset[r], one more rounding in T (offset: D values, T;
+ * NULL: none): the un-centring of a reading held in the frame of
+ * pmx_set_reference_centred, in the same kernel.  The homogeneous row and the
+ * normals are not offset. */
+int pmx_transform_reading_offset(pmx_ctx* ctx, const void* T_params, const void* offset, void* feat_out,
+                                 void* normals_out);
 /* T_iter after each completed iteration (keep_trace): count x rows x rows T */
 int pmx_loop_trace(pmx_ctx* ctx, int first, int count, void* out);
 /* Quantile window statistics of the device loop (no reference counterpart;

@@ -105,6 +105,23 @@ int pmx_icp_prepare(pmx_icp* icp, const void* reading, int rows, int64_t N, cons
 /* run up to n iterations; *done = 1 once a checker stopped the loop */
 int pmx_icp_iterate(pmx_icp* icp, int n, int* done);
 int pmx_icp_finish(pmx_icp* icp, void* T_out);
+/* the filtered reading moved by the last compute's result, T_out * readingFiltered,
+ * in the caller's frame: rows x n; *n the filtered reading's size
+ * (what transformation->compute(readingFiltered, T_out) returns for the
+ * features; capacity in T values, at least n * rows; feat_out NULL: *n and
+ * *rows alone, nothing is launched).  While the device still holds the
+ * filtered reading (the device loop, or the module calls without
+ * readingStepDataPointsFilters) nothing is uploaded: the device applies T_iter
+ * to its resident reading, which the chain keeps centred on the reference
+ * mean, and adds the mean back in the same kernel as one more separately
+ * rounded step (pmx_transform_reading_offset, include/pmx.h); after a finished
+ * device loop T_iter itself is read on the device.  Otherwise
+ * pmx_transform_cloud runs on the host copy of the filtered reading with the
+ * full T_out; the two agree within a few units in the last place of the
+ * largest coordinate.  With a borrowed reading (pmx_icp_compute's arrays) the
+ * host copy is the caller's array, which must then still be alive.
+ * PMX_ICP_RUNTIME_ERROR before any compute (a state error). */
+int pmx_icp_reading_transformed(pmx_icp* icp, void* feat_out, int64_t capacity, int64_t* n, int* rows);
 
 int pmx_icp_stats_get(const pmx_icp* icp, pmx_icp_stats* out);
 /* errorMinimizer->getCovariance() (PointMatcher.h:553, ErrorMinimizer.cpp:

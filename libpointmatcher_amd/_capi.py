@@ -194,6 +194,7 @@ EXPORTS = [
     "pmx_sampling_surface_normals", "pmx_voxel_grid", "pmx_keep_filter", "pmx_octree_grid",
     "pmx_normal_space", "pmx_covariance_sampling",
     "pmx_incidence_angles", "pmx_sphericality", "pmx_remove_sensor_bias", "pmx_transform_cloud",
+    "pmx_transform_reading", "pmx_transform_reading_offset",
 ]
 
 
@@ -291,6 +292,8 @@ def lib():
         l.pmx_transform_cloud.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_double)]
+        l.pmx_transform_reading.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pmx_transform_reading_offset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.pmx_sampling_surface_normals.argtypes = ([C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint]
                                                    + [C.c_void_p] * 6 + [C.POINTER(C.c_int64)] * 2)
@@ -1066,6 +1069,30 @@ class Context:
         out = np.zeros((count, 4), np.int64)
         self._chk(self._l.pmx_loop_diag(self.h, int(first), int(count), _ptr(out)))
         return out
+
+    def transform_reading(self, T=None, normals=False, offset=None):
+        """Transformation::compute on the resident reading (pmx_transform_reading):
+        T * (the reading as the context holds it), (N, rows) in set_reading's
+        order; nothing is uploaded.  T None: the finished device loop's T_iter,
+        read on the device.  normals: also the rotation block times the
+        resident reading normals, (N, rows - 1); (features, normals) is
+        returned.  offset (rows - 1 values): added to each coordinate after the
+        transform (pmx_transform_reading_offset)."""
+        P = self._arr(T) if T is not None else None
+        if P is not None and self.rows is not None and P.shape != (self.rows, self.rows):
+            raise InvalidParameter(f"T must be ({self.rows}, {self.rows}), not {P.shape}")
+        rows = self.rows or 4
+        of = np.empty((self.N, rows), self.dtype)
+        on = np.empty((self.N, rows - 1), self.dtype) if normals else None
+        if offset is None:
+            rc = self._l.pmx_transform_reading(self.h, _ptr(P), _ptr(of), _ptr(on))
+        else:
+            off = self._arr(offset).reshape(-1)
+            if off.shape[0] != rows - 1:
+                raise InvalidParameter(f"offset must have {rows - 1} values, not {off.shape[0]}")
+            rc = self._l.pmx_transform_reading_offset(self.h, _ptr(P), _ptr(off), _ptr(of), _ptr(on))
+        self._chk(rc)
+        return (of, on) if normals else of
 
     def loop_T(self, st):
         r = self.rows

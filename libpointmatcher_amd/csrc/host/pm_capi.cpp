@@ -162,6 +162,20 @@ void finish_impl(pmx_icp* icp, void* T_out) {
 }
 
 template <typename T>
+void reading_transformed_impl(pmx_icp* icp, void* feat_out, int64_t capacity, int64_t* n, int* rows) {
+    auto& I = get<T>(icp);
+    int r = 0;
+    const int64_t cnt = I.readingTransformedSize(&r);  // (throws before any compute)
+    if (n) *n = cnt;
+    if (rows) *rows = r;
+    if (!feat_out) return;  // (the size alone: nothing is launched)
+    if (capacity < 0 || (uint64_t)capacity < (uint64_t)cnt * (uint64_t)r)
+        throw InvalidParameter("pmx_icp_reading_transformed: capacity below n * rows");
+    const std::vector<T> out = I.readingTransformed();
+    if (!out.empty()) std::memcpy(feat_out, out.data(), sizeof(T) * out.size());
+}
+
+template <typename T>
 void covariance_impl(pmx_icp* icp, void* cov36) {
     auto& I = get<T>(icp);
     if (!I.errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
@@ -343,6 +357,14 @@ int pmx_icp_iterate(pmx_icp* icp, int n, int* done) {
 
 int pmx_icp_finish(pmx_icp* icp, void* T_out) {
     return guarded(icp, [&] { BOTH(icp, finish_impl<float>(icp, T_out), finish_impl<double>(icp, T_out)); });
+}
+
+int pmx_icp_reading_transformed(pmx_icp* icp, void* feat_out, int64_t capacity, int64_t* n, int* rows) {
+    if (!icp) return PMX_ICP_INVALID_PARAMETER;
+    return guarded(icp, [&] {
+        BOTH(icp, reading_transformed_impl<float>(icp, feat_out, capacity, n, rows),
+             reading_transformed_impl<double>(icp, feat_out, capacity, n, rows));
+    });
 }
 
 int pmx_icp_add_descriptor(pmx_icp* icp, int cloud, const char* name, int span, const void* values, int64_t n) {

@@ -2235,6 +2235,8 @@ void PointMatcher<T>::ICP::prepare(std::shared_ptr<const DataPoints> readingPtr,
                                    std::shared_ptr<const DataPoints> referencePtr,
                                    const TransformationParameters& T_init) {
     const DataPoints& referenceIn = *referencePtr;
+    filteredReading_.reset();  // (readingTransformed: the last compute's reading goes with its reference frame)
+    readingResident_ = loopOwnT_ = false;
     // ICP::compute, ICP.cpp:265-313
     if (!matcher) throw std::runtime_error("You must setup a matcher before running ICP");
     if (!errorMinimizer) throw std::runtime_error("You must setup an error minimizer before running ICP");
@@ -2304,6 +2306,8 @@ void PointMatcher<T>::ICP::prepareReading(std::shared_ptr<const DataPoints> read
     const DataPoints& reading = *readingPtr;
     elemReading_ = readingPtr;
     elemStep_ = elemNormalsPre_ = false;
+    filteredReading_.reset();
+    readingResident_ = loopOwnT_ = false;
     // T_refMean_dataIn = T_refIn_refMean^-1 * T_init (the inverse of a pure
     // translation is exact), ICP.cpp:345-346
     TransformationParameters inv((size_t)dim * dim, (T)0);
@@ -2318,6 +2322,8 @@ void PointMatcher<T>::ICP::prepareReading(std::shared_ptr<const DataPoints> read
         throw TransformationError("RigidTransformation: Error, rotation matrix is not orthogonal.");
     // transformations.apply(reading, T_refMean_dataIn): done on the device
     dev.check(pmx_set_reading(dev.ctx, reading.feat(), dim, reading.n, T_refMean_dataIn_.data()));
+    filteredReading_ = readingPtr;  // (readingTransformed: the device holds it in <refMean> until a step filter's upload)
+    readingResident_ = true;
     matcher->initReading(dev, reading);  // (per-reading matcher inputs: KDTreeVarDistMatcher's radii)
     uploadReadingNormals(reading);       // (SurfaceNormalOutlierFilter; rotated by T_refMean_dataIn on the device)
     keepReadingNoise(reading);
@@ -2756,6 +2762,7 @@ bool PointMatcher<T>::ICP::iterate(int n) {
     if (st.reason == 1) maxNumIterationsReached = true;
     if (st.done) iterate_ = false;
     if (rc != PMX_OK) dev.check(rc);  // the exception the loop raised
+    loopOwnT_ = st.done != 0;  // (readingTransformed reads the finished loop's T_iter on the device)
     // (stopped by a checker: the last iteration's match is still resident,
     // nothing has replaced it yet)
     if (st.done && fresh > 0) {
@@ -2779,6 +2786,7 @@ bool PointMatcher<T>::ICP::stepModules() {
         readingStepDataPointsFilters.apply(stepReading);
         elemReading_ = stepPtr;  // (the last iteration's is the one getErrorElements gathers from)
         elemStep_ = true;
+        readingResident_ = false;  // (the device now holds the step reading)
         TransformationParameters I((size_t)dim * dim, (T)0);
         for (int i = 0; i < dim; ++i) I[(size_t)i * dim + i] = 1;
         dev.check(pmx_set_reading(dev.ctx, stepReading.features.data(), dim, stepReading.n, I.data()));
@@ -2810,11 +2818,49 @@ bool PointMatcher<T>::ICP::stepModules() {
 template <typename T>
 typename PointMatcher<T>::TransformationParameters PointMatcher<T>::ICP::finish() {
     convergenceDuration = since<T>(t0_);
+    return fullTransform();
+}
+
+template <typename T>
+typename PointMatcher<T>::TransformationParameters PointMatcher<T>::ICP::fullTransform() const {
     const int dim = rows_;
     TransformationParameters tmp((size_t)dim * dim), out((size_t)dim * dim);
     dense::matmul(T_refIn_refMean_.data(), T_iter_.data(), dim, tmp.data());
     dense::matmul(tmp.data(), T_refMean_dataIn_.data(), dim, out.data());
     return out;  // ICP.cpp:448
+}
+
+template <typename T>
+int64_t PointMatcher<T>::ICP::readingTransformedSize(int* rows) const {
+    if (!filteredReading_ || rows_ == 0)
+        throw std::runtime_error("readingTransformed: no compute has run on this object (state error)");
+    if (rows) *rows = rows_;
+    return filteredReading_->n;
+}
+
+template <typename T>
+std::vector<T> PointMatcher<T>::ICP::readingTransformed(int64_t* n_out) {
+    readingTransformedSize();
+    const DataPoints& reading = *filteredReading_;
+    const int dim = rows_;
+    std::vector<T> out((size_t)dim * (size_t)reading.n);
+    if (n_out) *n_out = reading.n;
+    if (reading.n == 0) return out;
+    if (readingResident_) {
+        // T_refIn_refMean * (T_iter * resident): the mean added in the kernel
+        T mean[3] = {0, 0, 0};
+        for (int r = 0; r < dim - 1; ++r) mean[r] = T_refIn_refMean_[(size_t)r * dim + dim - 1];
+        dev.check(pmx_transform_reading_offset(dev.ctx, loopOwnT_ ? nullptr : T_iter_.data(), mean, out.data(),
+                                               nullptr));
+    } else {
+        const TransformationParameters Tf = fullTransform();
+        const int rc = pmx_transform_cloud(dev.device, dtype_of<T>(), reading.feat(), dim, reading.n, Tf.data(),
+                                           nullptr, 0, nullptr, 0, out.data(), nullptr, nullptr);
+        if (rc != PMX_OK)
+            throw std::runtime_error("readingTransformed: pmx error " + std::to_string(rc) + ": " +
+                                     pmx_last_error(nullptr));
+    }
+    return out;
 }
 
 template struct PointMatcher<float>;

@@ -317,6 +317,18 @@ struct PointMatcher {
         bool iterate(int n);
         bool deviceLoop = true;
         TransformationParameters finish();    // T_refIn_refMean * T_iter * T_refMean_dataIn
+        // The filtered reading moved by the last compute's result,
+        // finish() * readingFiltered, in the caller's frame: rows x n
+        // point-major (what transformation->compute(readingFiltered, T) gives).
+        // While the device still holds the filtered reading (no
+        // readingStepDataPointsFilters re-uploaded it) nothing is uploaded: the
+        // device applies T_iter to the resident reading in <refMean> (after a
+        // finished device loop its own T_iter, read on the device) and adds the
+        // reference mean in the same kernel (pmx_transform_reading_offset).
+        // Otherwise pmx_transform_cloud on the host copy of the filtered
+        // reading with the full T.  std::runtime_error before any prepare.
+        std::vector<T> readingTransformed(int64_t* n = nullptr);
+        int64_t readingTransformedSize(int* rows = nullptr) const;  // its n (and rows); the same exception
 
         // ICPSequence (PointMatcher.h:730-764, ICP.cpp:455-609): a map kept
         // resident on the device (centred, filtered and indexed once by
@@ -356,6 +368,13 @@ struct PointMatcher {
         // getErrorElements' sources (ErrorMinimizer::Elements): shared with the minimiser when the loop stops
         std::shared_ptr<const DataPoints> elemReading_, elemReference_;
         bool elemStep_ = false, elemNormalsPre_ = false;
+        // readingTransformed's sources: the filtered reading on the host
+        // (borrowed or owned as elemReading_), and whether the device still
+        // holds it in <refMean> (a step filter's re-upload replaces it)
+        std::shared_ptr<const DataPoints> filteredReading_;
+        bool readingResident_ = false;
+        bool loopOwnT_ = false;               // a device loop finished without error: its T_iter is on the device
+        TransformationParameters fullTransform() const;  // finish()'s product
         // the reading's "normals" to the device when a filter of the chain
         // reads them (after every reading upload)
         void uploadReadingNormals(const DataPoints& reading);

@@ -276,6 +276,7 @@ int pmx_ctx_create(int device, int dtype, pmx_ctx** out) {
         timed("normals", preload_normals);
         timed("setup", preload_setup);
         timed("ssn", preload_ssn);
+        timed("transform", preload_transform);
         preloaded = true;
     }
     // One small "iteration block" holds everything the host reads back per
@@ -325,7 +326,7 @@ int pmx_ctx_destroy(pmx_ctx* c) {
                     c->d_sel_more, c->d_gdesc, c->d_loop_T0, c->d_trace, c->d_diag, c->d_ticket, c->d_nbr,
                     c->d_spec, c->d_spec_keys, c->d_order, c->d_raw, c->d_bbox, c->d_occ, c->d_selx,
                     c->d_rob, c->d_rdev, c->d_radii, c->d_rd_p4, c->d_rd_sorted, c->d_rnrm,
-                    c->d_rnoise, c->d_ref_noise, c->d_ref_dens, c->d_elem, c->d_elem_inv};
+                    c->d_rnoise, c->d_ref_noise, c->d_ref_dens, c->d_elem, c->d_elem_inv, c->d_xout};
     side_finish(c);  // (the side stream may still be building levels)
     for (void* b : bufs)
         if (b) (void)hipFree(b);

@@ -600,6 +600,7 @@ int set_reading_impl(pmx_ctx* c, const T* feat, int rows, int64_t N, const T* T0
     c->has_radii = false;  // (a new reading: its radii, if any, follow)
     c->has_rnrm = false;   // (and its normals, pmx_set_reading_normals)
     c->has_rnoise = false; // (and its sensor noise, pmx_set_reading_noise)
+    c->loop_reading = false;  // (a finished loop's T_iter belongs to the reading it ran on: pmx_transform_reading)
     for (int i = 0; i < 16; ++i) c->T0[i] = (double)M0.m[i];
     // raw P4 reading (pack), then the slot order, then T_refMean_dataIn
     // (scratch and the resident reading kept across readings: ICPSequence

@@ -196,6 +196,10 @@ struct pmx_ctx {
     void* d_rd_p4 = nullptr;       // set_reading scratch: the packed reading before / after the slot sort
     void* d_rd_sorted = nullptr;
     size_t rd_p4_bytes = 0, rd_sorted_bytes = 0;
+    // pmx_transform_reading's download staging: rows x N point-major T in the
+    // caller's index order, then (256-byte aligned) the D x N normals
+    void* d_xout = nullptr;
+    size_t xout_bytes = 0;
     // KDTreeVarDistMatcher: per-point search radii in slot order (pmx_set_reading_radii)
     void* d_radii = nullptr;
     size_t radii_bytes = 0;
@@ -361,6 +365,7 @@ struct pmx_ctx {
     SpecSel spec_init{};  // (host staging of the reset)
     SpecSel* spec_now() const { return spec_on && loop_on ? d_spec : nullptr; }
     bool loop_begun = false;
+    bool loop_reading = false;    // the loop begun last ran on the current reading (pmx_set_reading clears it)
     pmx_loop_cfg loop_cfg{};
     LoopCfg loop_dev{};
     void* h_loop = nullptr;       // pinned: two copies of the status block (the batches in flight)

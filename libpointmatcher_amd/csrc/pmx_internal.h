@@ -408,6 +408,21 @@ struct XformArgs {
 template <typename T>
 void launch_transform_cloud(const T* feat, int rows, int64_t n, const XformArgs<T>& a, const T* desc, int stride,
                             T* feat_out, T* desc_out, hipStream_t st);
+// The same on a context's resident reading (pmx_transform_reading): rd / nrm
+// the records in slot order, order the slot -> index table (null: identity);
+// the outputs point-major in index order (rows and rows - 1 values per point).
+// Tdev (device; null: a.p) the rows x rows matrix read on the device; with
+// a.add_mean, mean[r] is added to coordinate r after the expression.
+template <typename T>
+struct XformReadingArgs {
+    T p[16];
+    T mean[3];
+    int add_mean;
+};
+template <typename T>
+void launch_transform_reading(const P4<T>* rd, const P4<T>* nrm, const int32_t* order, int rows, int64_t n,
+                              const XformReadingArgs<T>& a, const T* Tdev, T* feat_out, T* nrm_out, hipStream_t st);
+void preload_transform();
 // code-object preloads (one per translation unit, called by pmx_ctx_create)
 void preload_setup();
 void preload_ssn();

@@ -210,6 +210,7 @@ int loop_begin_impl(pmx_ctx* c, const pmx_loop_cfg* cfg_in, const T* T0) {
     c->shard_replay = false;
     c->spec_fresh = c->spec_on && sharded(c);  // (the first pick of an empty window misses)
     c->loop_begun = true;
+    c->loop_reading = true;
     return PMX_OK;
 }
 
@@ -567,6 +568,49 @@ int loop_trace_impl(pmx_ctx* c, int first, int count, void* out) {
     return PMX_OK;
 }
 
+// pmx_transform_reading (pmx_transform.hip transform_reading_kernel): the
+// resident reading's records through one kernel into the staging buffer in the
+// caller's index order, one download per output.  Tp null: the finished loop's
+// T_iter, read by the kernel from LoopState on the device (the launch follows
+// the loop's kernels on the context stream: no host copy, no wait before it).
+template <typename T>
+int transform_reading_impl(pmx_ctx* c, const T* Tp, const T* offset, void* feat_out, void* nrm_out) {
+    if (!c->d_rd || c->rows == 0) return fail(c, PMX_E_STATE, "pmx_set_reading must be called first");
+    if (nrm_out && !c->has_rnrm)
+        return fail(c, PMX_E_STATE, "pmx_transform_reading: no reading normals are set (pmx_set_reading_normals)");
+    const T* Tdev = nullptr;
+    if (!Tp) {
+        if (!c->loop_begun || !c->loop_done || c->loop_err || !c->loop_reading)
+            return fail(c, PMX_E_STATE,
+                        "pmx_transform_reading: no T_params, and no device loop has finished on this reading "
+                        "(or it stopped on an error)");
+        Tdev = ((const LoopState<T>*)c->d_loop)->Titer;
+    }
+    if (c->N == 0) return PMX_OK;
+    if (!feat_out) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    XformReadingArgs<T> a{};
+    if (Tp)
+        for (int e = 0; e < c->rows * c->rows; ++e) a.p[e] = Tp[e];
+    if (offset) {
+        a.add_mean = 1;
+        for (int r = 0; r < c->dim; ++r) a.mean[r] = offset[r];
+    }
+    const size_t fb = sizeof(T) * (size_t)c->rows * (size_t)c->N;
+    const size_t fa = (fb + 255) & ~(size_t)255;
+    const size_t nb = nrm_out ? sizeof(T) * (size_t)c->dim * (size_t)c->N : 0;
+    int rc;
+    if ((rc = ensure(c, &c->d_xout, &c->xout_bytes, fa + nb))) return rc;
+    T* d_f = (T*)c->d_xout;
+    T* d_n = nb ? (T*)((char*)c->d_xout + fa) : nullptr;
+    launch_transform_reading<T>((const P4<T>*)c->d_rd, nb ? (const P4<T>*)c->d_rnrm_p4 : nullptr,
+                                c->has_order ? c->d_order : nullptr, c->rows, c->N, a, Tdev, d_f, d_n, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(feat_out, d_f, fb, hipMemcpyDeviceToHost, c->stream));
+    if (nb) HIPCHK(c, hipMemcpyAsync(nrm_out, d_n, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMX_OK;
+}
+
 }  // namespace pmxc
 
 using namespace pmxc;
@@ -601,6 +645,21 @@ int pmx_loop_error_elements_prepare(pmx_ctx* c, pmx_elements_info* info) {
     if (!c || !info) return fail(c, PMX_E_BAD_PARAM, "null argument");
     (void)hipSetDevice(c->device);
     return DISPATCH(c, loop_elements_impl<float>(c, info), loop_elements_impl<double>(c, info));
+}
+
+int pmx_transform_reading_offset(pmx_ctx* c, const void* T_params, const void* offset, void* feat_out,
+                                 void* normals_out) {
+    if (!c) return fail(c, PMX_E_BAD_PARAM, "null argument");
+    (void)hipSetDevice(c->device);
+    return DISPATCH(c,
+                    transform_reading_impl<float>(c, (const float*)T_params, (const float*)offset, feat_out,
+                                                  normals_out),
+                    transform_reading_impl<double>(c, (const double*)T_params, (const double*)offset, feat_out,
+                                                   normals_out));
+}
+
+int pmx_transform_reading(pmx_ctx* c, const void* T_params, void* feat_out, void* normals_out) {
+    return pmx_transform_reading_offset(c, T_params, nullptr, feat_out, normals_out);
 }
 
 int pmx_loop_trace(pmx_ctx* c, int first, int count, void* out) {

@@ -114,6 +114,8 @@ def lib():
         l.pmx_icp_sequence_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                                C.POINTER(C.c_int)]
         l.pmx_icp_sequence_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+        l.pmx_icp_reading_transformed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int)]
         l.pmx_transformation_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         l.pmx_transformation_destroy.argtypes = [C.c_void_p]
         l.pmx_transformation_last_error.argtypes = [C.c_void_p]
@@ -409,6 +411,18 @@ class ICP:
     def finish(self):
         out = np.zeros((self.rows, self.rows), self.dtype)
         self._chk(self._l.pmx_icp_finish(self.h, _p(out)))
+        return out
+
+    def reading_transformed(self):
+        """The filtered reading moved by the last compute's result, (n, rows) in
+        the caller's frame (pmx_icp_reading_transformed): what
+        Transformation.compute(filtered_reading, T) returns, without the upload
+        while the device still holds the filtered reading.  Raises RuntimeError
+        before any compute."""
+        n, rows = C.c_int64(0), C.c_int(0)
+        self._chk(self._l.pmx_icp_reading_transformed(self.h, None, 0, C.byref(n), C.byref(rows)))
+        out = np.empty((n.value, rows.value), self.dtype)
+        self._chk(self._l.pmx_icp_reading_transformed(self.h, _p(out), out.size, C.byref(n), C.byref(rows)))
         return out
 
     # --- introspection
